@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the device-resident parse+filter hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2f|c2|c3|c4] [--configs LIST|none]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2f|c2|c3|c4] [--dump-outputs DIR]
+    python bench.py --full [...] [--configs LIST|none] [--no-cpu]
     torchrun --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+
+A plain run does what the headline figure needs and no more: it streams the headline's
+capture to the device, warms up (an untimed pass of the K steps, then the W warm-up steps:
+see measure), times the K steps, writes the last step's
+outputs if --dump-outputs is given (dump_outputs below: <name>.npy files, a fixed sample of a
+large batch, identical inputs from run to run), and prints the line with `value` and
+`ms_per_step`; `roofline`, `cpu_baseline` and `configs` stay empty. Everything else described
+below (the other workloads, the CPU baselines, the kernel passes behind the rooflines, the
+group-ingest and ring entries) runs with --full, which is the run the documents quote.
 
 --gpus N without a launcher (WORLD_SIZE unset) starts the N rank processes itself, before
 anything touches a GPU (subprocess, never exec), rank r on device r, rendezvous on
@@ -202,7 +212,9 @@ class Capture:
     """Per-rank capture streamed to the device, plus the statistics the roofline needs
     (computed per streamed range, so the capture is never whole on the host)."""
 
-    def __init__(self, ctx, wl, n_total, seed, lo, hi, chunk=1 << 20):
+    def __init__(self, ctx, wl, n_total, seed, lo, hi, chunk=1 << 20, stats=True):
+        """stats=False (a plain run, which reports no roofline): the capture is streamed
+        only, the byte and line counts stay 0."""
         cfg = wl["cfg"]
         self.desc_full, _ = synth.layout(cfg, n_total, seed)
         off_full = synth.desc_off(self.desc_full)
@@ -231,6 +243,9 @@ class Capture:
             rel = off_full[s:j] - b0
             lens = ln_full[s:j]
             self.run.upload_data(buf[int(rel[0]):int(rel[-1] + lens[-1])], int(off_full[s]) - base)
+            if not stats:
+                i = j
+                continue
             start = off_full[s:j] - base
             w = np.minimum(lens, 128)
             self.win_bytes += int(w.sum())
@@ -309,6 +324,94 @@ def record_write_stats_planes(run) -> tuple[int, int]:
     return stored, -(-stored // LINE)
 
 
+DUMP_TILES = 2048        # --dump-outputs: 64-packet tiles sampled from a larger batch (131072 packets)
+DUMP_PASS_IDX = 1 << 20  # --dump-outputs: entries of the pass list kept when it is longer
+DUMP_SEED = 0xD0B5
+
+
+def dump_sample(n: int) -> np.ndarray:
+    """Packet indices --dump-outputs keeps: every packet of a batch of up to DUMP_TILES tiles,
+    else the packets of DUMP_TILES whole 64-packet tiles drawn with a fixed seed (ascending)."""
+    nt = (n + 63) // 64
+    if nt <= DUMP_TILES:
+        return np.arange(n, dtype=np.int64)
+    tiles = np.sort(np.random.default_rng(DUMP_SEED).choice(nt, DUMP_TILES, replace=False)).astype(np.int64)
+    idx = (tiles[:, None] * 64 + np.arange(64, dtype=np.int64)[None, :]).reshape(-1)
+    return idx[idx < n]
+
+
+def _save(dirname: str, name: str, arr, dtype, rank: int, world: int) -> None:
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"),
+            np.ascontiguousarray(arr, dtype=dtype))
+
+
+def dump_outputs(dirname: str, ctx, run, last_set: int, flags: int, rank: int, world: int) -> None:
+    """--dump-outputs: what the last timed step left in its output set (set `last_set` of the
+    two a pipelined run alternates), as a caller of bt_parse_filter_device reads it. A batch
+    above DUMP_TILES tiles is written as a fixed sample of whole tiles (dump_sample; the same
+    packets for records, decisions and verdict bits) plus whole-batch figures of the small
+    outputs, so that two builds can be compared output for output within 64 MB:
+      sample_index  packet indices of the sample (float64)
+      records       bt_rec of each sampled packet as its 24 little-endian u32 words (float64)
+      decide        decision byte of each sampled packet (float32)
+      verdict       verdict bit of each sampled packet (float32)
+      decide_hist   count of every decision byte value over the whole batch (float64[256])
+      verdict_pass  set verdict bits over the whole batch (float64[1])
+      n_pass        length of the ordered pass list (float64[1])
+      pass_idx      the pass list, or DUMP_PASS_IDX evenly spaced entries of it (float64)
+      pass_idx_sum  sum of the whole pass list (float64[1], exact below 2^53)"""
+    d_rec, d_ver, d_dec, d_pidx, d_npass = (run.d_rec, run.d_ver, run.d_dec, run.d_pidx, run.d_npass) \
+        if last_set == 0 else run.alt
+    n = run.n
+    idx = dump_sample(n)
+    ctx.synchronize()
+    _save(dirname, "sample_index", idx, np.float64, rank, world)
+    if d_rec is not None and n:
+        buf = d_rec.download(np.empty(d_rec.nbytes, np.uint8))
+        if flags & abi.OPT_RECORDS_AOS:
+            rec = buf[: n * abi.BT_REC_BYTES].reshape(n, abi.BT_REC_BYTES)[idx]
+        elif flags & abi.OPT_RECORDS_PLANES or len(idx) == n:
+            rec = abi.untile_records(buf, n, planes=bool(flags & abi.OPT_RECORDS_PLANES))[idx]
+        else:   # tiles stand alone in the packed layout: unpack the sampled ones only
+            tiles = np.unique(idx // 64)
+            part = np.ascontiguousarray(buf[: ((n + 63) // 64) * 6144].reshape(-1, 6144)[tiles]).reshape(-1)
+            rec = abi.untile_records(part, len(idx))
+        del buf
+        _save(dirname, "records", np.ascontiguousarray(rec).view("<u4"), np.float64, rank, world)
+    if d_dec is not None:
+        dec = d_dec.download(np.zeros(max(n, 1), np.uint8))[:n]
+        _save(dirname, "decide", dec[idx], np.float32, rank, world)
+        _save(dirname, "decide_hist", np.bincount(dec, minlength=256), np.float64, rank, world)
+    if d_ver is not None:
+        ver = d_ver.download(np.zeros(max((n + 63) // 64, 1), np.uint64))
+        bits = np.unpackbits(ver.view(np.uint8), bitorder="little")[:n]
+        _save(dirname, "verdict", bits[idx], np.float32, rank, world)
+        _save(dirname, "verdict_pass", [int(bits.sum(dtype=np.int64))], np.float64, rank, world)
+    if d_pidx is not None:
+        npass = int(d_npass.download(np.zeros(1, np.uint32))[0])
+        pidx = d_pidx.download(np.zeros(max(npass, 1), np.uint32))[:npass]
+        _save(dirname, "n_pass", [npass], np.float64, rank, world)
+        _save(dirname, "pass_idx_sum", [int(pidx.sum(dtype=np.uint64))], np.float64, rank, world)
+        if npass > DUMP_PASS_IDX:
+            pidx = pidx[np.linspace(0, npass - 1, DUMP_PASS_IDX).astype(np.int64)]
+        _save(dirname, "pass_idx", pidx, np.float64, rank, world)
+
+
+def dump_extract_outputs(dirname: str, ex, rank: int, world: int) -> None:
+    """--dump-outputs of the user-protocol extractor: status byte (float32), each field's
+    value (float64, [fields, packets]) and the span-byte image (float32) of the sampled
+    packets (dump_sample), plus the count of every status value over the whole batch."""
+    status, values, image = ex.fetch()
+    idx = dump_sample(ex.n)
+    _save(dirname, "sample_index", idx, np.float64, rank, world)
+    _save(dirname, "status", status[idx], np.float32, rank, world)
+    _save(dirname, "status_hist", np.bincount(status, minlength=256), np.float64, rank, world)
+    _save(dirname, "values", values[:, idx], np.float64, rank, world)
+    if image is not None:
+        _save(dirname, "image", image[idx], np.float32, rank, world)
+
+
 def load_traffic(path, key, n):
     """Per-launch HBM bytes from rocprofv3 PMC passes (tools/pmc_traffic.py), if the
     committed figure was measured on these kernel sources and this batch size."""
@@ -359,7 +462,8 @@ def measure(name, wl, args, ctx, flags, dist, rank, world, strong):
         del d_all
     else:
         lo, hi, n_total = 0, args.packets, args.packets
-    cap = Capture(ctx, wl, n_total, seed, lo, hi)
+    full = args.full   # a plain run times the steps only: no roofline bookkeeping, no kernel pass
+    cap = Capture(ctx, wl, n_total, seed, lo, hi, stats=full)
     run, n = cap.run, cap.n
     filt = wl["filters"] is not None
     if filt:
@@ -376,9 +480,12 @@ def measure(name, wl, args, ctx, flags, dist, rank, world, strong):
     # bytes); the warm-up follows it, so the GPU goes from the warm-up straight into the
     # timed region instead of idling through seconds of host work (a first pass after
     # such an idle spell ran 3-5 % slower than a second one, profiles/r02/ab/warm_order.txt).
-    run.run()
-    n_pass = run.n_pass() if filt else 0
-    if run.d_rec is None or not n:
+    # A plain run (no --full) needs none of that bookkeeping and goes straight to its warm-up;
+    # its pass count is read from the last timed step's outputs.
+    if full:
+        run.run()
+    n_pass = run.n_pass() if filt and full else 0
+    if run.d_rec is None or not n or not full:
         rec_bytes, rec_lines = 0, 0
     elif flags & abi.OPT_RECORDS_AOS:   # 96-B bt_rec per packet, contiguous
         rec_bytes = n * abi.BT_REC_BYTES
@@ -391,7 +498,10 @@ def measure(name, wl, args, ctx, flags, dist, rank, world, strong):
     # pairs the kernel pass uses), then the W warm-up steps in exactly the timed form, so
     # the timed pass repeats the launches the GPU ran last (with the kernel-event pass
     # last, a timed pass of 20 steps ran ~0.2 ms longer than 20 x its steady step)
-    ctx.time_device2(run.batch, outs, args.steps, mode | abi.TIME_KERNEL_EVENTS)
+    # A plain run keeps that untimed pass of the K steps (in the timed form, it needs no events):
+    # with the W = 5 warm-up steps alone after the capture upload, 20 timed c2f steps ran at
+    # 0.372 ms against 0.340 ms after 25 or 100 of them, and 0.338 ms in the full form.
+    ctx.time_device2(run.batch, outs, args.steps, (mode | abi.TIME_KERNEL_EVENTS) if full else timed_mode)
     if args.warmup:
         ctx.time_device2(run.batch, outs, args.warmup, timed_mode)
 
@@ -414,6 +524,14 @@ def measure(name, wl, args, ctx, flags, dist, rank, world, strong):
     barrier()
     tb = time.perf_counter()
     step_s = (t1 - t0) / args.steps
+    last_set = (args.steps - 1) % len(outs)   # step i wrote output set i % len(outs)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, run, last_set, flags, rank, world)
+    if not full and filt and n:   # a plain run's pass count: what the last timed step left
+        d_npass = run.d_npass if last_set == 0 else run.alt[4]
+        n_pass = int(d_npass.download(np.zeros(1, np.uint32))[0]) if d_npass is not None else 0
+    # --full from here to the roofline; a plain run has no kernel pass (tk, main_ms = None)
+    # and no roofline, and shares the gather over ranks and the entry's assembly below.
     # The main kernel's duration: the same K steps again, each main kernel between an
     # event pair recorded by its own dispatch. Those events cost the GPU ~9 us per step
     # (tools/calib/boundary.hip), so they stay out of the timed region above. A PAYLOAD
@@ -422,8 +540,10 @@ def measure(name, wl, args, ctx, flags, dist, rank, world, strong):
     # waits behind (1.35 ms between the events against 0.89 ms of kernel in the rocprofv3 trace
     # of the same run): its kernel pass runs the compaction after each kernel instead.
     kmode = 0 if wl.get("payload") else mode
-    tk = tm if args.kernel_events_in_timed else ctx.time_device2(run.batch, outs if kmode else outs[:1], args.steps,
-                                                                 kmode | abi.TIME_KERNEL_EVENTS)
+    tk = None
+    if full:
+        tk = tm if args.kernel_events_in_timed else ctx.time_device2(run.batch, outs if kmode else outs[:1],
+                                                                     args.steps, kmode | abi.TIME_KERNEL_EVENTS)
 
     # algorithmic bytes of one main-kernel launch (SURVEY §8(d), R = the stored slabs):
     # min(len,128) header read + 8 B descriptor (0 for fixed stride) + R + 1 B decision
@@ -434,7 +554,7 @@ def measure(name, wl, args, ctx, flags, dist, rank, world, strong):
     # record lines + decisions + verdict words
     floor_read = cap.need_lines * LINE + (0 if wl["fixed"] else 8 * n)
     floor_write = rec_lines * LINE + ((n + (n + 63) // 64 * 8) if filt else 0)
-    main_ms = tk.main_ms
+    main_ms = tk.main_ms if tk is not None else None
     mine = {"step_s": step_s, "main_ms": main_ms, "n": n, "algo": algo, "pass": n_pass,
             "host_ms": 1e3 * (ta - t0), "tail_ms": 1e3 * (t1 - ta), "barrier_ms": 1e3 * (tb - t1)}
     ranks = [mine]
@@ -442,8 +562,34 @@ def measure(name, wl, args, ctx, flags, dist, rank, world, strong):
         ranks = [None] * world
         dist.all_gather_object(ranks, mine)
     step_max = max(r["step_s"] for r in ranks)
-    kms_max = max(r["main_ms"] for r in ranks)
     value = n_job / step_max / 1e6
+    roof = None
+    if full:
+        roof = main_roofline(name, wl, args, flags, n, filt, algo, rec_bytes, floor_read, floor_write, tm, tk)
+    timing = timing_entry(tm, tk, step_s, args, host_call_ms=round(mine["host_ms"], 4),
+                          tail_sync_ms=round(mine["tail_ms"], 4),
+                          closing_barrier_ms_max_over_ranks=round(max(r["barrier_ms"] for r in ranks), 4),
+                          pipelined=piped, output_sets=len(outs))
+    out = {"workload": wl["name"], "value": round(value, 2), "unit": "Mpps", "ms_per_step": round(step_max * 1e3, 4),
+           "scaling": "strong" if strong else "weak", "packets_per_gpu": n, "packets_total": n_job,
+           "pass_fraction": round(n_pass / n, 4) if filt and n else None, "roofline": roof,
+           "roofline_aggregate": aggregate_roofline(ranks, world) if full else None, "timing": timing}
+    if world > 1 and full:
+        out["per_rank"] = [{"rank": i, "packets": r["n"], "ms_per_step": round(r["step_s"] * 1e3, 4),
+                            "kernel_ms": round(r["main_ms"], 4),
+                            "frac": round(r["algo"] / (r["main_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+                           for i, r in enumerate(ranks)]
+        out["kernel_ms_max_over_ranks"] = round(max(r["main_ms"] for r in ranks), 4)
+    sample = cap.cpu_sample(wl, seed, args.cpu_sample) if full and rank == 0 and not args.no_cpu else None
+    run.free()
+    return out, sample
+
+
+def main_roofline(name, wl, args, flags, n, filt, algo, rec_bytes, floor_read, floor_write, tm, tk) -> dict:
+    """`roofline` of a parse+filter entry (--full): the algorithmic bytes of one main-kernel launch
+    over the kernel pass's mean duration, the PMC traffic if it was measured on these sources, and
+    the 128-B-line floor."""
+    main_ms = tk.main_ms
     achieved = algo / (main_ms * 1e-3) / 1e9
     key = wl.get("traffic_key", name if not wl.get("payload") else None)
     traffic_rec, traffic_src = load_traffic(args.traffic_json, key, n) if key else (None, "PAYLOAD variant")
@@ -465,89 +611,90 @@ def measure(name, wl, args, ctx, flags, dist, rank, world, strong):
     if traffic_rec:
         roof["traffic_read_per_packet"] = traffic_rec.get("read_per_packet")
         roof["traffic_write_per_packet"] = traffic_rec.get("write_per_packet")
+    return roof
+
+
+def timing_entry(tm, tk, step_s, args, **mine) -> dict:
+    """`timing` of an entry, plain or --full: the timed pass's own breakdown and wall time, the
+    caller's figures (`mine`), the steps of the untimed pass that ran before the W warm-up steps
+    (see measure), and, when a kernel pass ran (tk, --full only), that pass."""
     timing = tm.as_dict()
-    timing.update({"wall_ms": round(1e3 * step_s * args.steps, 4), "host_call_ms": round(mine["host_ms"], 4),
-                   "tail_sync_ms": round(mine["tail_ms"], 4),
-                   "closing_barrier_ms_max_over_ranks": round(max(r["barrier_ms"] for r in ranks), 4),
-                   "wall_over_span": round(step_s * args.steps * 1e3 / tm.span_ms, 4) if tm.span_ms > 0 else None,
-                   "pipelined": piped, "output_sets": len(outs),
-                   "kernel_events_in_timed_region": bool(args.kernel_events_in_timed)})
-    timing["kernel_pass"] = {k: v for k, v in tk.as_dict().items()
-                             if k in ("span_ms", "main_ms", "main_min_ms", "main_max_ms", "lead_ms", "gap_ms")}
-    timing["kernel_pass"]["ms_per_step"] = round(tk.span_ms / args.steps, 4)
-    out = {"workload": wl["name"], "value": round(value, 2), "unit": "Mpps", "ms_per_step": round(step_max * 1e3, 4),
-           "scaling": "strong" if strong else "weak", "packets_per_gpu": n, "packets_total": n_job,
-           "pass_fraction": round(n_pass / n, 4) if filt and n else None, "roofline": roof,
-           "roofline_aggregate": aggregate_roofline(ranks, world), "timing": timing}
-    if world > 1:
-        out["per_rank"] = [{"rank": i, "packets": r["n"], "ms_per_step": round(r["step_s"] * 1e3, 4),
-                            "kernel_ms": round(r["main_ms"], 4),
-                            "frac": round(r["algo"] / (r["main_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-                           for i, r in enumerate(ranks)]
-        out["kernel_ms_max_over_ranks"] = round(kms_max, 4)
-    sample = cap.cpu_sample(wl, seed, args.cpu_sample) if rank == 0 and not args.no_cpu else None
-    run.free()
-    return out, sample
+    timing["wall_ms"] = round(1e3 * step_s * args.steps, 4)
+    timing.update(mine)
+    timing.update({"wall_over_span": round(step_s * args.steps * 1e3 / tm.span_ms, 4) if tm.span_ms > 0 else None,
+                   "kernel_events_in_timed_region": bool(args.kernel_events_in_timed),
+                   "untimed_prepass_steps": args.steps})
+    if tk is not None:
+        timing["kernel_pass"] = {k: v for k, v in tk.as_dict().items()
+                                 if k in ("span_ms", "main_ms", "main_min_ms", "main_max_ms", "lead_ms", "gap_ms")}
+        timing["kernel_pass"]["ms_per_step"] = round(tk.span_ms / args.steps, 4)
+    return timing
 
 
 def measure_extract(name, wl, args, ctx, rank):
     """The user-protocol extractor (bt_extract_tile) over a device-resident capture: one
     step = one bt_extract_device pass over the batch (N=1 entry)."""
     seed = synth.SEEDS[wl["cfg"]] + rank
-    cap = Capture(ctx, wl, args.packets, seed, 0, args.packets)
+    full = args.full   # a plain run times the steps only (see measure)
+    cap = Capture(ctx, wl, args.packets, seed, 0, args.packets, stats=full)
     n, fields = cap.n, wl["extract"]
     ex = abi.DeviceExtract(ctx, None, None, n, fields, batch=cap.run.batch)
-    ex.run()
-    ok = int((ex.fetch()[0] == 0).sum())   # host bookkeeping before the warm-up (see measure)
+    if full:
+        ex.run()
+        ok = int((ex.fetch()[0] == 0).sum())   # host bookkeeping before the warm-up (see measure)
     for _ in range(args.warmup):
         ex.run()
-    ex.time(args.steps)   # untimed: creates the per-launch event pairs
+    if full:
+        ex.time(args.steps)   # untimed: creates the per-launch event pairs
+    else:
+        ex.time(args.steps, abi.TIME_KERNEL_EVENTS if args.kernel_events_in_timed else 0)   # untimed (see measure)
     ctx.synchronize()
     t0 = time.perf_counter()
     tm = ex.time(args.steps, abi.TIME_KERNEL_EVENTS if args.kernel_events_in_timed else 0)
     ctx.synchronize()
     t1 = time.perf_counter()
     step_s = (t1 - t0) / args.steps
-    tk = tm if args.kernel_events_in_timed else ex.time(args.steps)   # the kernel pass (see measure)
+    if args.dump_outputs:
+        dump_extract_outputs(args.dump_outputs, ex, rank, 1)
+    if not full:   # a plain run's parsed count: what the last timed step left
+        ok = int((ex.d_status.download(np.zeros(max(n, 1), np.uint8))[:n] == 0).sum())
+    tk = None
+    if full:
+        tk = tm if args.kernel_events_in_timed else ex.time(args.steps)   # the kernel pass (see measure)
     span, nf = ex.span, len(fields)
-    # algorithmic bytes: the [0, span) prefix read + status byte + one u64 per field + the
-    # span-byte image; the floor reads the 128-B lines of those prefixes
-    lens = synth.desc_len(cap.desc)
-    starts = synth.desc_off(cap.desc) if not wl["fixed"] else np.arange(n, dtype=np.int64) * cap.stride
-    rd = int(np.minimum(lens, span).sum())
-    lines, _ = unique_lines(starts, np.minimum(lens, span))
-    wr = n * (1 + 8 * nf + span)
-    algo = rd + wr
-    floor = lines * LINE + sum(-(-b // LINE) * LINE for b in (n, 8 * nf * n, span * n))
-    achieved = algo / (tk.main_ms * 1e-3) / 1e9
-    traffic_rec, traffic_src = load_traffic(args.traffic_json, name, n)
-    roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4),
-            "traffic": traffic_rec["traffic"] if traffic_rec else None, "traffic_source": traffic_src,
-            "traffic_bytes_per_packet": round(traffic_rec["traffic"] / n, 2) if traffic_rec else None,
-            "traffic_floor": floor, "traffic_floor_bytes_per_packet": round(floor / n, 2),
-            "kernel": "bt_extract_tile", "kernel_ms": round(tk.main_ms, 4),
-            "kernel_ms_min": round(tk.main_min_ms, 4), "kernel_ms_max": round(tk.main_max_ms, 4),
-            "algorithmic_bytes_per_packet": round(algo / n, 2), "kernel_mpps": round(n / (tk.main_ms * 1e-3) / 1e6, 1),
-            "gpu_span_ms_per_step": round(tm.span_ms / args.steps, 4)}
-    if traffic_rec:
-        roof["traffic_read_per_packet"] = traffic_rec.get("read_per_packet")
-        roof["traffic_write_per_packet"] = traffic_rec.get("write_per_packet")
-    timing = tm.as_dict()
-    timing.update({"wall_ms": round(1e3 * step_s * args.steps, 4),
-                   "wall_over_span": round(step_s * args.steps * 1e3 / tm.span_ms, 4) if tm.span_ms > 0 else None,
-                   "kernel_events_in_timed_region": bool(args.kernel_events_in_timed)})
-    timing["kernel_pass"] = {k: v for k, v in tk.as_dict().items()
-                             if k in ("span_ms", "main_ms", "main_min_ms", "main_max_ms", "lead_ms", "gap_ms")}
-    timing["kernel_pass"]["ms_per_step"] = round(tk.span_ms / args.steps, 4)
     out = {"workload": wl["name"], "value": round(n / step_s / 1e6, 2), "unit": "Mpps",
            "ms_per_step": round(step_s * 1e3, 4), "scaling": "weak", "packets_per_gpu": n, "packets_total": n,
            "parsed_fraction": round(ok / n, 4), "table": [list(f) for f in fields], "span": span,
-           "roofline": roof,
-           "roofline_aggregate": aggregate_roofline([{"algo": algo, "main_ms": tk.main_ms, "step_s": step_s}], 1),
-           "timing": timing,
-           "published": "parser_example: 25 us to parse its one 17-byte packet (README.md:1110; BASELINE.md §1)"}
-    sample = cap.cpu_sample(wl, seed, args.cpu_sample) if rank == 0 and not args.no_cpu else None
+           "roofline": None, "roofline_aggregate": None, "timing": timing_entry(tm, tk, step_s, args)}
+    if full:
+        # algorithmic bytes: the [0, span) prefix read + status byte + one u64 per field + the
+        # span-byte image; the floor reads the 128-B lines of those prefixes
+        lens = synth.desc_len(cap.desc)
+        starts = synth.desc_off(cap.desc) if not wl["fixed"] else np.arange(n, dtype=np.int64) * cap.stride
+        rd = int(np.minimum(lens, span).sum())
+        lines, _ = unique_lines(starts, np.minimum(lens, span))
+        wr = n * (1 + 8 * nf + span)
+        algo = rd + wr
+        floor = lines * LINE + sum(-(-b // LINE) * LINE for b in (n, 8 * nf * n, span * n))
+        achieved = algo / (tk.main_ms * 1e-3) / 1e9
+        traffic_rec, traffic_src = load_traffic(args.traffic_json, name, n)
+        roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4),
+                "traffic": traffic_rec["traffic"] if traffic_rec else None, "traffic_source": traffic_src,
+                "traffic_bytes_per_packet": round(traffic_rec["traffic"] / n, 2) if traffic_rec else None,
+                "traffic_floor": floor, "traffic_floor_bytes_per_packet": round(floor / n, 2),
+                "kernel": "bt_extract_tile", "kernel_ms": round(tk.main_ms, 4),
+                "kernel_ms_min": round(tk.main_min_ms, 4), "kernel_ms_max": round(tk.main_max_ms, 4),
+                "algorithmic_bytes_per_packet": round(algo / n, 2),
+                "kernel_mpps": round(n / (tk.main_ms * 1e-3) / 1e6, 1),
+                "gpu_span_ms_per_step": round(tm.span_ms / args.steps, 4)}
+        if traffic_rec:
+            roof["traffic_read_per_packet"] = traffic_rec.get("read_per_packet")
+            roof["traffic_write_per_packet"] = traffic_rec.get("write_per_packet")
+        out.update(roofline=roof,
+                   roofline_aggregate=aggregate_roofline([{"algo": algo, "main_ms": tk.main_ms, "step_s": step_s}], 1),
+                   published="parser_example: 25 us to parse its one 17-byte packet (README.md:1110; BASELINE.md §1)")
+    sample = cap.cpu_sample(wl, seed, args.cpu_sample) if full and rank == 0 and not args.no_cpu else None
     ex.free()
     cap.run.free()
     return out, sample
@@ -873,6 +1020,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline's timed steps: the other workloads (--configs), the CPU "
+                         "baselines, the kernel passes and rooflines, the group-ingest and ring entries")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last step computed as DIR/<name>.npy "
+                         "(float32 / float64; a fixed sample of a large batch, see dump_outputs)")
     ap.add_argument("--config", default="c2f", choices=sorted(WORKLOADS), help="the headline workload")
     ap.add_argument("--configs", default="auto",
                     help="comma list of extra workloads for the `configs` object (suffix _strong: strong "
@@ -911,6 +1064,17 @@ def main():
         print(json.dumps(res), flush=True)
         return
 
+    if not args.full:   # say so where an option asks for something only --full measures
+        if args.configs not in ("auto", "none"):
+            ap.error(f"--configs {args.configs} needs --full (a plain run times the headline only)")
+        unused = [o for o, given in (("--cpu-seconds", args.cpu_seconds != ap.get_default("cpu_seconds")),
+                                     ("--cpu-sample", args.cpu_sample != ap.get_default("cpu_sample")),
+                                     ("--group-ingest-packets",
+                                      args.group_ingest_packets not in (0, ap.get_default("group_ingest_packets"))))
+                  if given]
+        if unused and os.environ.get("RANK", "0") == "0" and ("WORLD_SIZE" in os.environ or args.gpus == 1):
+            print(f"bench.py: {', '.join(unused)} only matter{'s' if len(unused) == 1 else ''} with --full; "
+                  f"this plain run measures no CPU baseline and no ingest entry", file=sys.stderr, flush=True)
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             sys.exit(spawn_ranks(args.gpus))
@@ -943,7 +1107,9 @@ def main():
             sys.exit("--payload needs a filtering workload")
         head.update(filters=[{"type": abi.PAYLOAD, "expr": args.payload, "priority": 9}] + head["filters"],
                     name=head["name"] + f" + PAYLOAD /{args.payload}/ first", payload=args.payload)
-    if args.configs == "auto":
+    if not args.full:   # a plain run: the headline's timed steps only
+        extra = []
+    elif args.configs == "auto":
         extra = ["c2", "c3", "c4", "c1", "c3_payload"] if world == 1 else ["c3", "c3_strong"]
     elif args.configs == "none":
         extra = []
@@ -955,7 +1121,9 @@ def main():
     jobs = [("__head__", args.config, head, args.strong)] + \
            [(c, c.replace("_strong", ""), dict(WORKLOADS[c.replace("_strong", "")]), c.endswith("_strong"))
             for c in extra]
+    dump_dir = args.dump_outputs
     for key, name, wl, strong in jobs:
+        args.dump_outputs = dump_dir if key == "__head__" else None   # the headline's outputs only
         if wl.get("extract"):
             res, sample = measure_extract(name, wl, args, ctx, rank)
         else:
@@ -966,7 +1134,7 @@ def main():
     # other ranks wait at the barrier below meanwhile (north_star: "timed on the node's own host
     # cores ... in the same run", at every GPU count)
     cpus = host_cpus()
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         attach_cpu_baselines(results, samples, cpus, world,
                              lambda smp, wl, sec, c: (cpu_baseline_extract if wl.get("extract") else cpu_baseline)(
                                  smp, wl, sec, c),
@@ -976,7 +1144,7 @@ def main():
     # device-resident timing: the other ranks wait at a barrier meanwhile
     if dist is not None:
         dist.barrier()
-    if rank == 0 and args.group_ingest_packets > 0 and args.configs != "none":
+    if rank == 0 and args.full and args.group_ingest_packets > 0 and args.configs != "none":
         try:
             results["zero_copy_group"] = (measure_group_ingest(world, args.group_ingest_packets) if world == 1
                                           else group_ingest_isolated(world, args.group_ingest_packets,
@@ -1040,6 +1208,7 @@ def build_line(results: dict, args, world: int, devices: dict) -> dict:
         "warmup": args.warmup,
         "ms_per_step": h["ms_per_step"],
         "higher_is_better": True,
+        "full": bool(getattr(args, "full", False)),   # False: roofline, cpu_baseline and configs are left empty
         "scaling": h["scaling"],
         "vs_baseline": None,
         "dtype": "u8",

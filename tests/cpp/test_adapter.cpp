@@ -1010,7 +1010,7 @@ int main(int argc, char** argv) {
         std::printf("%s (%d failures)\n", ok && !g_fail ? "ALL OK" : "FAILED", g_fail);
         return ok && !g_fail ? 0 : 1;
     }
-    const char* plugin_so = argc > 1 ? argv[1] : "beatrice_amd/libgpu_parse_filter_plugin.so";
+    const char* plugin_so = argc > 1 ? argv[1] : "oracle/_ref/libgpu_parse_filter_plugin.so";
     Capture c3 = capture(3, 20000, 0x5EED0003), c4 = capture(4, 12000, 0x5EED0004), fz = capture(9, 30000, 0x5EED0009);
     const std::vector<Spec> headline = {{"proto", T::PROTOCOL, "udp", 3, true, 0},
                                         {"net", T::IP_RANGE, "10.0.0.0/8", 2, true, 0},

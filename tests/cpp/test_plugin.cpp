@@ -415,12 +415,12 @@ static bool records_case(const char* so, const char* data_path, const char* desc
 int main(int argc, char** argv) {
     if (argc == 5 && std::strcmp(argv[1], "records") == 0) {
         const char* so = std::getenv("BT_PLUGIN_SO") ? std::getenv("BT_PLUGIN_SO")
-                                                     : "beatrice_amd/libgpu_parse_filter_plugin.so";
+                                                     : "oracle/_ref/libgpu_parse_filter_plugin.so";
         const bool ok = records_case(so, argv[2], argv[3], argv[4]);
         std::printf(ok && !g_fail ? "ALL OK\n" : "FAILURES\n");
         return ok && !g_fail ? 0 : 1;
     }
-    const char* so = argc > 1 ? argv[1] : "beatrice_amd/libgpu_parse_filter_plugin.so";
+    const char* so = argc > 1 ? argv[1] : "oracle/_ref/libgpu_parse_filter_plugin.so";
     int ndev = 0;
     if (bt_device_count(&ndev) != BT_OK || ndev == 0) {
         std::printf("no GPU\n");

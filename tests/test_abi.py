@@ -114,7 +114,7 @@ def test_plugin_library_exports_the_plugin_abi():
     /root/reference/src/PluginManager.cpp:67-68) and every C hook its header declares; linked
     -z nodelete (~PluginManager dlcloses before destroying plugins, :26-34); and the only
     reference symbol it takes from the host process is Packet's out-of-line constructor."""
-    so = os.path.join(ROOT, "beatrice_amd", "libgpu_parse_filter_plugin.so")
+    so = os.path.join(ROOT, "oracle", "_ref", "libgpu_parse_filter_plugin.so")
     assert os.path.exists(so), "plugin not built"
     hdr = open(os.path.join(ROOT, "include", "beatrice_gpu_plugin.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)

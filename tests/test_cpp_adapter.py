@@ -7,13 +7,15 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "test_adapter")
+REF_DIR = os.path.join(ROOT, "oracle", "_ref")   # everything compiled against the reference
+BIN = os.path.join(REF_DIR, "test_adapter")
+PLUGIN_SO = os.path.join(REF_DIR, "libgpu_parse_filter_plugin.so")
 
 
 @pytest.mark.gpu
 def test_cpp_adapter_matches_reference():
-    assert os.path.exists(BIN), "tests/cpp/test_adapter not built (make -C tests/cpp in the build container)"
-    r = subprocess.run([BIN, os.path.join(ROOT, "beatrice_amd", "libgpu_parse_filter_plugin.so")],
+    assert os.path.exists(BIN), "oracle/_ref/test_adapter not built (make -C oracle ref)"
+    r = subprocess.run([BIN, PLUGIN_SO],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     print(r.stdout)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
@@ -25,9 +27,9 @@ def test_plugin_in_the_reference_pipeline():
     """tests/cpp/test_plugin.cpp: the plugin driven through PluginManager's call sequence
     from an in-memory capture backend — flush thread, per-packet errors, ordered verdict
     sink — against the reference PacketFilter."""
-    b = os.path.join(ROOT, "tests", "cpp", "test_plugin")
-    assert os.path.exists(b), "tests/cpp/test_plugin not built (make -C tests/cpp in the build container)"
-    r = subprocess.run([b, os.path.join(ROOT, "beatrice_amd", "libgpu_parse_filter_plugin.so")],
+    b = os.path.join(REF_DIR, "test_plugin")
+    assert os.path.exists(b), "oracle/_ref/test_plugin not built (make -C oracle ref)"
+    r = subprocess.run([b, PLUGIN_SO],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     print(r.stdout)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
@@ -48,9 +50,9 @@ def test_plugin_sink_records_equal_reference_goldens(cap, tmp_path):
         p = tmp_path / f"{k}.bin"
         g[k].tofile(p)
         paths.append(str(p))
-    b = os.path.join(ROOT, "tests", "cpp", "test_plugin")
-    assert os.path.exists(b), "tests/cpp/test_plugin not built (make -C tests/cpp in the build container)"
-    env = dict(os.environ, BT_PLUGIN_SO=os.path.join(ROOT, "beatrice_amd", "libgpu_parse_filter_plugin.so"))
+    b = os.path.join(REF_DIR, "test_plugin")
+    assert os.path.exists(b), "oracle/_ref/test_plugin not built (make -C oracle ref)"
+    env = dict(os.environ, BT_PLUGIN_SO=PLUGIN_SO)
     r = subprocess.run([b, "records", *paths], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     print(r.stdout)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]

@@ -19,7 +19,7 @@ from conftest import GOLDEN
 from golden_util import compare_decisions
 
 pytestmark = pytest.mark.gpu
-CAPTURE_BIN = os.path.join(os.path.dirname(GOLDEN), "cpp", "test_capture")
+CAPTURE_BIN = os.path.join(os.path.dirname(ol.REF_SO), "test_capture")
 
 
 def _run_ring(ctx, ring, bs, nb, filters, records=True):
@@ -82,7 +82,7 @@ def test_packed_ring_1m_matches_oracle(gpu_ctx, cfg):
 
 
 def test_cpp_stage_on_kernel_written_ring(tmp_path):
-    assert os.path.exists(CAPTURE_BIN), "tests/cpp/test_capture not built (make -C tests/cpp)"
+    assert os.path.exists(CAPTURE_BIN), "oracle/_ref/test_capture not built (make -C oracle ref)"
     g = np.load(os.path.join(GOLDEN, "ring_lo.npz"))
     bs, nb = (int(x) for x in g["geometry"])
     img = tmp_path / "ring.bin"
@@ -94,7 +94,7 @@ def test_cpp_stage_on_kernel_written_ring(tmp_path):
 
 
 def test_cpp_stage_synthetic_ring():
-    assert os.path.exists(CAPTURE_BIN), "tests/cpp/test_capture not built (make -C tests/cpp)"
+    assert os.path.exists(CAPTURE_BIN), "oracle/_ref/test_capture not built (make -C oracle ref)"
     r = subprocess.run([CAPTURE_BIN, "stage-synth"], capture_output=True, text=True, timeout=600)
     print(r.stdout)
     assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
@@ -104,7 +104,7 @@ def test_cpp_stage_per_gpu_fanout_rings():
     """Per-GPU ring sharding: a capture split by flow into 2 and 3 TPACKET_V3 ring
     images, one GpuPacketFilter + GpuTpacketStage per ring, drained concurrently, each ring's
     decisions equal to the reference PacketFilter's and every frame seen once."""
-    assert os.path.exists(CAPTURE_BIN), "tests/cpp/test_capture not built (make -C tests/cpp)"
+    assert os.path.exists(CAPTURE_BIN), "oracle/_ref/test_capture not built (make -C oracle ref)"
     r = subprocess.run([CAPTURE_BIN, "stage-fanout"], capture_output=True, text=True, timeout=600)
     print(r.stdout)
     assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

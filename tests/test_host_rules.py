@@ -83,7 +83,7 @@ class _Layer(ctypes.Structure):
 
 
 def test_gpu_batch_layers_bounded_for_any_record():
-    so = os.path.join(ROOT, "beatrice_amd", "libgpu_parse_filter_plugin.so")
+    so = os.path.join(ROOT, "oracle", "_ref", "libgpu_parse_filter_plugin.so")
     assert os.path.exists(so), "plugin not built"
     L = ctypes.CDLL(so, mode=os.RTLD_LAZY | os.RTLD_GLOBAL)
     L.gpu_batch_layers.restype = ctypes.c_uint32

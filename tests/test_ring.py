@@ -251,14 +251,14 @@ def test_fanout_hash_rings_split_by_flow(rings):
             s.close()
 
 
-CAPTURE_BIN = os.path.join(os.path.dirname(GOLDEN), "cpp", "test_capture")
+CAPTURE_BIN = os.path.join(os.path.dirname(ol.REF_SO), "test_capture")
 
 
 @pytest.mark.skipif(not _can_raw(), reason="no CAP_NET_RAW: cannot open an AF_PACKET ring")
 def test_cpp_backend_on_loopback():
     """GpuAfPacketBackend (ICaptureBackend drop-in) on a live TPACKET_V3 ring on lo."""
     import subprocess
-    assert os.path.exists(CAPTURE_BIN), "tests/cpp/test_capture not built (make -C tests/cpp)"
+    assert os.path.exists(CAPTURE_BIN), "oracle/_ref/test_capture not built (make -C oracle ref)"
     r = subprocess.run([CAPTURE_BIN, "backend"], capture_output=True, text=True, timeout=120)
     print(r.stdout)
     assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

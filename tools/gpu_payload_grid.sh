@@ -6,7 +6,7 @@ OUT=${OUT:-gpurun_out/payload_grid}
 mkdir -p "$OUT"
 for r in $(seq ${ROUNDS:-2}); do
   for g in ${GRIDS:-0 3 -1}; do
-    BT_PAYLOAD_GRID=$g timeout -k 10 300 python bench.py --config c3_payload --configs none --no-cpu \
+    BT_PAYLOAD_GRID=$g timeout -k 10 300 python bench.py --full --config c3_payload --configs none --no-cpu \
       --group-ingest-packets 0 > "$OUT/grid_${g}_$r.json" 2> "$OUT/grid_${g}_$r.err" || { tail -20 "$OUT/grid_${g}_$r.err"; exit 3; }
     python3 tools/summ.py "$OUT/grid_${g}_$r.json" | grep head | sed "s/^/grid $g: /"
   done

@@ -8,7 +8,7 @@ CFGS=${*:-c2f c2 c3 c4 c1}
 mkdir -p $OUT
 export TMPDIR=/tmp
 for cfg in $CFGS; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$cfg -o run -- python3 bench.py --config $cfg --configs none --steps ${PROF_STEPS:-100} --warmup 3 --no-cpu > $OUT/${cfg}_bench_under_rocprof.json 2>&1 || exit 4
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$cfg -o run -- python3 bench.py --full --config $cfg --configs none --steps ${PROF_STEPS:-100} --warmup 3 --no-cpu > $OUT/${cfg}_bench_under_rocprof.json 2>&1 || exit 4
   timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_${cfg}_fetch -o run -- python3 bench.py --config $cfg --configs none --steps 3 --warmup 1 --no-cpu > /dev/null 2>&1 || exit 4
   timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_${cfg}_write -o run -- python3 bench.py --config $cfg --configs none --steps 3 --warmup 1 --no-cpu > /dev/null 2>&1 || exit 4
   python3 tools/pmc_traffic.py --fetch $OUT/pmc_${cfg}_fetch --write $OUT/pmc_${cfg}_write --config $cfg --out $OUT/traffic.json | cut -c1-200

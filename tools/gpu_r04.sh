@@ -66,7 +66,7 @@ case $CASE in
     for rep in 1 2; do
       timeout -k 10 300 tools/calib/gather_c4 > "$OUT/gather_c4_$rep.txt" 2>&1 || { cat "$OUT/gather_c4_$rep.txt"; exit 3; }
       cat "$OUT/gather_c4_$rep.txt"
-      timeout -k 10 200 python3 bench.py --configs none --no-cpu --steps 20 --warmup 3 --config c4 > "$OUT/c4_$rep.json" 2>&1 || exit 3
+      timeout -k 10 200 python3 bench.py --full --configs none --no-cpu --steps 20 --warmup 3 --config c4 > "$OUT/c4_$rep.json" 2>&1 || exit 3
       python3 tools/summ.py "$OUT/c4_$rep.json"
     done ;;
   plugin-hot)
@@ -105,7 +105,7 @@ case $CASE in
     summ_ab "$OUT/ab.jsonl" ;;
   kernel-ab)
     bash tools/ab_cmd.sh "$OUT" ${REPS:-3} "prev|BT_LIB_PATH=$PWD/beatrice_amd/ab/prev/libbeatrice_gpu.so|" "cur||" \
-      -- python bench.py --configs c2,c3,c4 --no-cpu --group-ingest-packets 0 --steps 20 || exit 1
+      -- python bench.py --full --configs c2,c3,c4 --no-cpu --group-ingest-packets 0 --steps 20 || exit 1
     python3 - "$OUT/ab.jsonl" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

@@ -43,7 +43,7 @@ case $1 in
       for cfg in ${AB_CFGS:-c2f}; do
         for v in base env; do
           e=""; [ $v = env ] && e="${AB_ENV:?AB_ENV=NAME=VALUE}"
-          env $e timeout -k 10 150 python3 bench.py --config $cfg --configs none --no-cpu --steps 50 --warmup 5 \
+          env $e timeout -k 10 150 python3 bench.py --full --config $cfg --configs none --no-cpu --steps 50 --warmup 5 \
             > "$OUT/envab_${r}_${cfg}_$v.json" 2> "$OUT/envab.err" || fail "envab $cfg $v" $? "$OUT/envab.err"
           python3 - "$OUT/envab_${r}_${cfg}_$v.json" "$cfg $v" "$r" <<'PY'
 import json, sys
@@ -60,7 +60,7 @@ PY
       for v in c2 c2f c2f:records c2f:records,decide c2f:records,verdict; do
         cfg=${v%%:*}; outs=${v#*:}
         extra=""; [ "$outs" != "$v" ] && extra="--outputs $outs"
-        timeout -k 10 120 python3 bench.py --config $cfg --configs none --no-cpu --steps 50 --warmup 5 $extra \
+        timeout -k 10 120 python3 bench.py --full --config $cfg --configs none --no-cpu --steps 50 --warmup 5 $extra \
           > "$OUT/split_${r}_${v//[:,]/_}.json" 2> "$OUT/split.err" || fail "split $v" $? "$OUT/split.err"
         python3 - "$OUT/split_${r}_${v//[:,]/_}.json" "$v" "$r" <<'PY'
 import json, sys
@@ -90,7 +90,7 @@ PY
       for cfg in ${AB_CFGS:-c2f}; do
         for v in base ${AB_NAMES:?AB_NAMES}; do
           L=$PWD/beatrice_amd/libbeatrice_gpu.so; [ $v != base ] && L=$PWD/beatrice_amd/ab/$v/libbeatrice_gpu.so
-          BT_LIB_PATH=$L timeout -k 10 200 python bench.py --configs none --config $cfg --steps 50 --warmup 3 --no-cpu \
+          BT_LIB_PATH=$L timeout -k 10 200 python bench.py --full --configs none --config $cfg --steps 50 --warmup 3 --no-cpu \
             > "$OUT/abn_${cfg}_${v}_$r.json" 2> "$OUT/abn.err" || fail "abn $cfg $v" $? "$OUT/abn.err"
           python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); r=d['roofline']; print(sys.argv[2], sys.argv[3], sys.argv[4], 'step', d['ms_per_step'], 'kern', r['kernel_ms'], 'frac', r['frac'])" \
             "$OUT/abn_${cfg}_${v}_$r.json" $r $cfg $v | tee -a "$OUT/abn.txt"

@@ -8,8 +8,8 @@
 #   bounds  the same suite on the BT_DEBUG_BOUNDS build (beatrice_amd/dbg, make -C
 #           beatrice_amd/csrc debug): every kernel access checked   -> $OUT/pytest_bounds.log
 #   smoke   __graft_entry__.smoke()                                   -> $OUT/smoke.log
-#   bench   the default `python bench.py` line                       -> $OUT/bench_default.json
-#   multi   2- and 4-rank rehearsals on the one device (bench.py --gpus N spawning its
+#   bench   the `python bench.py --full` line (every config)         -> $OUT/bench_default.json
+#   multi   2- and 4-rank rehearsals on the one device (bench.py --full --gpus N spawning its
 #           ranks, BT_BENCH_DEVICE=0)                                -> $OUT/bench_{2,4}rank_one_gpu.json
 #   prof    rocprofv3 kernel stats + PMC traffic (tools/gpu_prof.sh) -> $OUT/prof/
 #   sq      SQ counters of the main kernels (tools/gpu_sq.sh)        -> $OUT/sq.txt
@@ -41,11 +41,11 @@ for step in $STEPS; do
       timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || fail smoke $? "$OUT/smoke.log"
       tail -1 "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 600 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || fail bench $? "$OUT/bench_default.err"
+      timeout -k 10 600 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || fail bench $? "$OUT/bench_default.err"
       python3 tools/summ.py "$OUT/bench_default.json" ;;
     multi)
       for n in 2 4; do
-        BT_BENCH_DEVICE=0 timeout -k 10 600 python bench.py --gpus $n \
+        BT_BENCH_DEVICE=0 timeout -k 10 600 python bench.py --full --gpus $n \
           > "$OUT/bench_${n}rank_one_gpu.json" 2> "$OUT/bench_${n}rank.err" || fail multi$n $? "$OUT/bench_${n}rank.err"
         python3 tools/summ.py "$OUT/bench_${n}rank_one_gpu.json"
       done ;;

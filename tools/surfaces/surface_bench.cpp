@@ -732,7 +732,7 @@ int main(int argc, char** argv) {
     uint32_t n2 = 1u << 22, n3 = 1u << 21;
     double seconds = 3.0;
     int threads = usable_cpus();
-    const char* so = "beatrice_amd/libgpu_parse_filter_plugin.so";
+    const char* so = "oracle/_ref/libgpu_parse_filter_plugin.so";
     std::vector<size_t> chunks = {16384, 65536};
     std::vector<int> members = {1, 2, 4};
     std::string data_node = "none";
