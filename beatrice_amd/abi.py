@@ -79,6 +79,11 @@ OPT_NO_LEAN_PCIE = 0x8000
 OPT_MAPPED_GATHER_SPARSE = 0x10000
 OPT_NO_LEAN_HOST = 0x20000
 OPT_PAYLOAD_DFA = 0x40000
+OPT_PAYLOAD_EXTENDED = 0x80000   # PAYLOAD slots: \b \B, POSIX classes and wide DFAs on the GPU too
+# bt_payload_dfa_compile_ex flags
+DFA_NO_PAIRS = 0x1
+DFA_NO_BITPAR = 0x2
+DFA_EXTENDED = 0x4
 TIME_KERNEL_EVENTS = 0x1
 TIME_PIPELINED = 0x2
 
@@ -263,6 +268,7 @@ def lib() -> ctypes.CDLL:
         "bt_ring_stage_tpv3": (ctypes.c_int, [vp, ctypes.POINTER(Tpv3Ring), u32, u32, ctypes.POINTER(RingStageOpts),
                                               vp, vp, vp, vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "bt_payload_dfa_compile": (ctypes.c_int, [ctypes.c_char_p, vp, u32, ctypes.POINTER(u32)]),
+        "bt_payload_dfa_compile_ex": (ctypes.c_int, [ctypes.c_char_p, u32, vp, u32, ctypes.POINTER(u32)]),
         "bt_payload_dfa_search": (ctypes.c_int, [vp, vp, u32]),
         "bt_payload_dfa_eval": (ctypes.c_int, [vp, vp, u32]),
         "bt_format_records": (ctypes.c_int, [vp, vp, u32, u32, vp, u64, ctypes.POINTER(u64), vp]),
@@ -840,19 +846,26 @@ def ring_release_tpv3(ring: np.ndarray, block_size: int, n_blocks: int, first: i
     _check(lib().bt_ring_release_tpv3(ctypes.byref(r), first, count))
 
 
-def payload_dfa(expr: str):
+def payload_dfa(expr: str, flags: int = 0):
     """bt_payload_dfa_compile: the DFA blob (bytes), None when the expression is outside
-    the GPU subset (it stays on the host), or raises BtError if std::regex rejects it."""
+    the GPU subset (it stays on the host), or raises BtError if std::regex rejects it.
+    flags (DFA_*): bt_payload_dfa_compile_ex with them; DFA_EXTENDED widens the subset."""
     L = lib()
     e = expr.encode("latin-1")
     size = ctypes.c_uint32()
-    rc = L.bt_payload_dfa_compile(e, None, 0, ctypes.byref(size))
+
+    def compile_(buf, cap):
+        if flags:
+            return L.bt_payload_dfa_compile_ex(e, flags, buf, cap, ctypes.byref(size))
+        return L.bt_payload_dfa_compile(e, buf, cap, ctypes.byref(size))
+
+    rc = compile_(None, 0)
     if rc == 11:
         return None
     if rc:
         raise BtError(rc, f"bt_payload_dfa_compile({expr!r}) = {rc}")
     buf = ctypes.create_string_buffer(size.value)
-    _check(L.bt_payload_dfa_compile(e, buf, size.value, ctypes.byref(size)))
+    _check(compile_(buf, size.value))
     return buf.raw
 
 

@@ -390,6 +390,33 @@ __device__ __forceinline__ uint32_t bitpar_fast(const uint8_t* blob, const uint3
     return (H & F) ? 1u : 0u;
 }
 
+// The wide form (bt_regex_dfa.cpp "The wide blob"; BT_DFA_EXTENDED): a DFA of 255..4,096 live
+// states, so the state ids are 16 bits and the table is always indexed through the byte
+// classes. Four window bytes per turn from two aligned dwords of the lane's row, as the byte
+// DFA's loop below reads them (the same row reads, so inside the row for the same reason);
+// their classes do not depend on the state and are read ahead of the chain, which is then one
+// 16-bit LDS read per byte. A state q < K indexes next[q * C + c] inside the K * C table; a
+// sink (K match, K + 1 none possible) is never used as an index.
+__device__ __forceinline__ uint32_t wide_walk(const uint8_t* blob, const uint32_t* row, uint32_t staged_sh,
+                                              uint32_t L) {
+    const uint32_t C = *reinterpret_cast<const uint16_t*>(blob + 2);
+    const uint32_t K = *reinterpret_cast<const uint16_t*>(blob + 4);
+    uint32_t q = *reinterpret_cast<const uint16_t*>(blob + 6);
+    const uint8_t* cls = blob + 12;
+    const uint8_t* endacc = cls + 256;
+    const uint16_t* next = reinterpret_cast<const uint16_t*>(endacc + ((K + 3u) & ~3u));
+    const uint32_t dw = staged_sh >> 2, sh = staged_sh & 3u;
+    for (uint32_t i = 0; i < L && q < K; i += 4u) {
+        const uint32_t w = __builtin_amdgcn_alignbyte(row[dw + (i >> 2) + 1u], row[dw + (i >> 2)], sh);
+        const uint32_t m = min(4u, L - i);
+        const uint32_t c[4] = {cls[w & 0xFFu], cls[(w >> 8) & 0xFFu], cls[(w >> 16) & 0xFFu], cls[w >> 24]};
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k)
+            if (k < m && q < K) q = next[q * C + c[k]];
+    }
+    return q >= K ? (q == K ? 1u : 0u) : (uint32_t)endacc[q];
+}
+
 // `reuse`: the 16-B chunks of the frame's header window (from its 16-B-aligned start) that round
 // A left in the row (4 in descriptor mode with whole 64-B windows, else 0). The window's chunks
 // among them are moved down the row instead of read again: their lines were read a tile ago and
@@ -466,6 +493,7 @@ __device__ __forceinline__ uint32_t eval_payload(const MainArgs& a, const uint8_
         default: return bitpar_walk<uint64_t, false>(blob, row, staged_sh, L, rdw);
         }
     }
+    if (K == 0xFFFEu) return wide_walk(blob, row, staged_sh, L);   // the wide form (wave-uniform too)
     const uint32_t C = *reinterpret_cast<const uint16_t*>(blob + 2);
     uint32_t q = blob[4];
     if (q >= K) return q == K ? 1u : 0u;

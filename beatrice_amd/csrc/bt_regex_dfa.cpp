@@ -15,13 +15,30 @@
 //   * character sets follow libstdc++ exactly as measured (`.` = all but \n \r; \s
 //     = 09-0d, 20; \w / \d ASCII; ranges compared as signed char).
 //
-// Anything outside the modelled subset — backreferences, lookaheads, \b \B, \c \u,
+// Anything outside the default subset — backreferences, lookaheads, \b \B, \c \u,
 // POSIX [[:classes:]], escapes of letters libstdc++ treats idiosyncratically, more
 // than 255 DFA states — returns BT_E_NOT_IMPLEMENTED and the filter stays on the
 // host (std::regex), as before. Only patterns std::regex itself accepts reach here
 // (the filter compiler probes first), so the parser never needs error recovery for
 // patterns the reference rejects. Agreement with std::regex is fuzzed in
 // tests/cpp/test_regex_dfa.cpp.
+//
+// BT_DFA_EXTENDED widens the subset by three things that are regular all the same; a
+// pattern the default subset takes compiles to the same bytes with or without the flag:
+//   * \b and \B: assertions on the pair (previous byte, next byte), where "word" is
+//     \w's set and the neighbour before position 0 and after the window's last byte
+//     counts as non-word. An assertion stays pending in the NFA set until the next byte
+//     (or the end) is known, so a DFA state becomes the pair (NFA set, was the last
+//     consumed byte a word byte) — plus "no byte consumed yet" for the initial state,
+//     where ^ may still stand behind a pending \b. On byte c the pending assertions are
+//     resolved first (\b holds iff the two word classes differ), then c is consumed; a
+//     match that completes during the resolution sends the state to the ACCEPT sink on
+//     that byte; endacc resolves them against the end of the input. The result is an
+//     ordinary DFA in the layout below. Such patterns never take the bit-parallel form.
+//   * POSIX classes inside brackets, [[:alpha:]] .. [[:xdigit:]] and libstdc++'s
+//     [[:d:]] [[:w:]] [[:s:]], as the C locale defines them (all below 0x80; w = alnum
+//     and _). Collating symbols [[.x.]] and equivalence classes [[=x=]] stay on the host.
+//   * up to 4,096 subset states; more than 254 live ones give the wide blob below.
 //
 // Blob layout (4-B aligned, little endian), shared by the host executor below and
 // the kernel (bt_kernels.hip, eval_payload). States 0..K-1 are live; K is the ACCEPT
@@ -37,6 +54,18 @@
 //   u8  clsp[256]         pairs only: byte -> class of the two-byte table
 //   u8  pair[K * P * P]   pairs only: the state after two bytes (a sink after the first
 //                         stays), so the walk's dependent chain is half as long
+//
+// The wide blob (BT_DFA_EXTENDED, 255 .. 4,096 live states): 16-bit state ids, always
+// through byte classes, no two-byte table. Its first half-word is a tag no state count
+// reaches (as the bit-parallel form's 0xFFFF below), so no reader takes it for the above.
+//   u16 0xFFFE, u16 C     C byte classes (<= 256)
+//   u16 K, u16 init       live states 0..K-1, sinks K (ACCEPT) and K+1 (DEAD) as above
+//   u8  empty, u8 0 x3    empty = match on the empty input
+//   u8  cls[256]          at byte 12
+//   u8  endacc[K] (pad 4) at byte 268
+//   u16 next[K * C]       the walk: q = next[q * C + cls[b]] until q >= K
+// A wide blob larger than the 16 KiB one block's LDS pool holds is not produced
+// (BT_E_NOT_IMPLEMENTED: the pattern stays on the host).
 #include <algorithm>
 #include <bitset>
 #include <cstring>
@@ -53,12 +82,15 @@ using Set = std::bitset<256>;
 
 constexpr int kMaxNfa = 6000;
 constexpr int kMaxDfa = 255;
+constexpr int kMaxDfaExtended = 4096;       // BT_DFA_EXTENDED: 16 KiB / (2 classes x 2 B)
+constexpr uint16_t kWideMagic = 0xFFFE;     // the wide blob's tag (layout above)
+constexpr uint32_t kWideBlobMax = 16384;    // the kernel's LDS pool (bt_device.h kDfaPoolMax)
 constexpr int kMaxRepeat = 100;   // payload windows are <= 100 bytes
 
 // ------------------------------------------------------------------ parse -> AST
 
 struct Node {
-    enum T { SET, CAT, ALT, REP, BOL, EOL, EMPTY } t;
+    enum T { SET, CAT, ALT, REP, BOL, EOL, EMPTY, WORDB, NWORDB } t;
     Set set;
     std::vector<int> kids;
     int lo = 0, hi = 0;   // REP: hi < 0 = unbounded
@@ -68,8 +100,9 @@ struct Unsupported {};
 
 class Parser {
 public:
-    explicit Parser(const std::string& p) : p_(p) {}
+    explicit Parser(const std::string& p, bool extended = false) : p_(p), ext_(extended) {}
     std::vector<Node> nodes;
+    static Set word_set() { return word(); }
 
     int parse() {
         const int r = disjunction();
@@ -79,6 +112,7 @@ public:
 
 private:
     const std::string& p_;
+    const bool ext_;   // BT_DFA_EXTENDED: \b \B and POSIX classes are parsed, not refused
     size_t i_ = 0;
 
     bool more() const { return i_ < p_.size(); }
@@ -123,6 +157,13 @@ private:
             if (more() && (peek() == '*' || peek() == '+' || peek() == '?' || peek() == '{'))
                 throw Unsupported{};   // quantified assertion
             return add(Node{c == '^' ? Node::BOL : Node::EOL});
+        }
+        if (ext_ && c == '\\' && i_ + 1 < p_.size() && (p_[i_ + 1] == 'b' || p_[i_ + 1] == 'B')) {
+            const bool neg = p_[i_ + 1] == 'B';
+            i_ += 2;
+            if (more() && (peek() == '*' || peek() == '+' || peek() == '?' || peek() == '{'))
+                throw Unsupported{};   // quantified assertion (std::regex rejects it itself)
+            return add(Node{neg ? Node::NWORDB : Node::WORDB});
         }
         int a = atom();
         while (more()) {   // libstdc++ accepts stacked quantifiers (a**): apply each in turn
@@ -180,6 +221,28 @@ private:
     static Set digit() { return range('0', '9'); }
     static Set word() { return range('0', '9') | range('A', 'Z') | range('a', 'z') | range('_', '_'); }
     static Set space() { return range(9, 13) | range(' ', ' '); }
+
+    // [:name:] in the C locale, as std::regex_traits<char>::lookup_classname / isctype
+    // classify bytes there (nothing at or above 0x80 is in any class)
+    static bool posix_class(const std::string& name, Set& s) {
+        const Set upper = range('A', 'Z'), lower = range('a', 'z'), alpha = upper | lower;
+        const Set punct = range(33, 47) | range(58, 64) | range(91, 96) | range(123, 126);
+        if (name == "alpha") s = alpha;
+        else if (name == "digit" || name == "d") s = digit();
+        else if (name == "alnum") s = alpha | digit();
+        else if (name == "w") s = word();
+        else if (name == "upper") s = upper;
+        else if (name == "lower") s = lower;
+        else if (name == "space" || name == "s") s = space();
+        else if (name == "blank") s = range(9, 9) | range(' ', ' ');
+        else if (name == "punct") s = punct;
+        else if (name == "print") s = range(32, 126);
+        else if (name == "graph") s = range(33, 126);
+        else if (name == "cntrl") s = range(0, 31) | range(127, 127);
+        else if (name == "xdigit") s = digit() | range('A', 'F') | range('a', 'f');
+        else return false;
+        return true;
+    }
 
     static int hexval(unsigned char c) {
         if (c >= '0' && c <= '9') return c - '0';
@@ -244,9 +307,20 @@ private:
                 ++i_;
                 break;
             }
-            if (c == '[') throw Unsupported{};   // [[:alpha:]] and friends
             int lo = -1;
             Set cls;
+            if (c == '[' && i_ + 1 < p_.size() && (p_[i_ + 1] == ':' || p_[i_ + 1] == '.' || p_[i_ + 1] == '=')) {
+                // [[:alpha:]] and friends; [[.x.]] and [[=x=]] stay on the host
+                if (!ext_ || p_[i_ + 1] != ':') throw Unsupported{};
+                const size_t end = p_.find(":]", i_ + 2);
+                if (end == std::string::npos || !posix_class(p_.substr(i_ + 2, end - i_ - 2), cls)) throw Unsupported{};
+                i_ = end + 2;
+                if (more() && peek() == '-' && i_ + 1 < p_.size() && p_[i_ + 1] != ']') throw Unsupported{};
+                s |= cls;
+                first = false;
+                continue;
+            }
+            if (c == '[' && !ext_) throw Unsupported{};   // as before the flag: every '[' inside brackets
             ++i_;
             if (c == '\\') {
                 int single = 0;
@@ -338,7 +412,7 @@ private:
 // ------------------------------------------------------------------ AST -> NFA
 
 struct NState {
-    enum T : uint8_t { SET, EPS, SPLIT, BOL, EOL, MATCH } t;
+    enum T : uint8_t { SET, EPS, SPLIT, BOL, EOL, MATCH, WORDB, NWORDB } t;
     int set_id = -1;
     int out = -1, out1 = -1;
 };
@@ -347,6 +421,7 @@ class Nfa {
 public:
     std::vector<NState> st;
     std::vector<Set> sets;
+    bool word_assertions = false;   // a \b or \B somewhere (BT_DFA_EXTENDED only)
 
     int make(NState::T t) {
         if ((int)st.size() >= kMaxNfa) throw Unsupported{};
@@ -373,6 +448,13 @@ public:
         case Node::EOL: {
             const int s = make(n.t == Node::BOL ? NState::BOL : NState::EOL), e = make(NState::EPS);
             st[s].out = e;
+            return {s, e};
+        }
+        case Node::WORDB:
+        case Node::NWORDB: {
+            const int s = make(n.t == Node::WORDB ? NState::WORDB : NState::NWORDB), e = make(NState::EPS);
+            st[s].out = e;
+            word_assertions = true;
             return {s, e};
         }
         case Node::CAT: {
@@ -436,8 +518,11 @@ public:
         throw Unsupported{};
     }
 
-    // epsilon closure; BOL edges only when bol, EOL edges only when eol
-    void closure(std::vector<int>& set, bool bol, bool eol) const {
+    // epsilon closure; BOL edges only when bol, EOL edges only when eol. Word assertions
+    // stay pending (kept in the set, not passed) unless the bytes on both sides are known:
+    // wb = kBoundary passes \b edges, kNoBoundary \B edges.
+    enum { kPending = 0, kBoundary = 1, kNoBoundary = 2 };
+    void closure(std::vector<int>& set, bool bol, bool eol, int wb = kPending) const {
         std::vector<char> seen(st.size(), 0);
         std::vector<int> stack(set.begin(), set.end());
         set.clear();
@@ -453,6 +538,8 @@ public:
             case NState::SPLIT: stack.push_back(n.out); stack.push_back(n.out1); break;
             case NState::BOL: if (bol) stack.push_back(n.out); break;
             case NState::EOL: if (eol) stack.push_back(n.out); break;
+            case NState::WORDB: if (wb == kBoundary) stack.push_back(n.out); break;
+            case NState::NWORDB: if (wb == kNoBoundary) stack.push_back(n.out); break;
             default: break;
             }
         }
@@ -470,11 +557,11 @@ struct Dfa {
     int n_classes = 0, init = 0;
     uint8_t cls[256];
     std::vector<uint8_t> acc;
-    std::vector<uint8_t> next;   // [state][class]
+    std::vector<uint16_t> next;   // [state][class]
 };
 
-Dfa build_dfa(const std::string& pattern) {
-    Parser ps(pattern);
+Dfa build_dfa(const std::string& pattern, bool extended) {
+    Parser ps(pattern, extended);
     const int root = ps.parse();
     Nfa nfa;
     auto frag = nfa.build(ps.nodes, root);
@@ -484,11 +571,14 @@ Dfa build_dfa(const std::string& pattern) {
 
     // byte classes: bytes with the same membership in every set are interchangeable
     Dfa d;
+    const bool wa = nfa.word_assertions;   // then a class is all word bytes or none
+    const Set word = Parser::word_set();
     {
         std::map<std::vector<bool>, int> sig;
         for (int b = 0; b < 256; ++b) {
-            std::vector<bool> v(nfa.sets.size());
+            std::vector<bool> v(nfa.sets.size() + (wa ? 1 : 0));
             for (size_t k = 0; k < nfa.sets.size(); ++k) v[k] = nfa.sets[k].test(b);
+            if (wa) v[nfa.sets.size()] = word.test(b);
             auto it = sig.find(v);
             if (it == sig.end()) it = sig.emplace(v, (int)sig.size()).first;
             d.cls[b] = (uint8_t)it->second;
@@ -504,30 +594,50 @@ Dfa build_dfa(const std::string& pattern) {
     std::vector<int> init{start};
     nfa.closure(init, true, false);
 
-    std::map<std::vector<int>, int> ids;
+    // A DFA state: the NFA set and, with word assertions pending in it, what they will be
+    // resolved against: bit 0 = the last consumed byte was a word byte, bit 1 = no byte
+    // consumed yet (the initial state only: ^ still holds behind a pending \b). Without
+    // word assertions the context is always 0 and the states are the sets alone.
+    enum { kPrevWord = 1, kAtStart = 2 };
+    const int max_states = extended ? kMaxDfaExtended : kMaxDfa;
+    std::map<std::pair<int, std::vector<int>>, int> ids;
     std::vector<std::vector<int>> sets;
-    auto intern = [&](const std::vector<int>& s) {
-        auto it = ids.find(s);
+    std::vector<int> context;
+    auto intern = [&](const std::vector<int>& s, int cx) {
+        auto it = ids.find({cx, s});
         if (it != ids.end()) return it->second;
-        if ((int)sets.size() >= kMaxDfa) throw Unsupported{};
-        ids.emplace(s, (int)sets.size());
+        if ((int)sets.size() >= max_states) throw Unsupported{};
+        ids.emplace(std::make_pair(cx, s), (int)sets.size());
         sets.push_back(s);
+        context.push_back(cx);
         return (int)sets.size() - 1;
     };
-    d.init = intern(init);
+    d.init = intern(init, wa ? kAtStart : 0);
     for (size_t q = 0; q < sets.size(); ++q) {
         for (int c = 0; c < d.n_classes; ++c) {
+            const bool w = word.test(rep[c]);
+            std::vector<int> from = sets[q];
+            bool matched = false;
+            if (wa) {   // the pending assertions, now that the byte on their right is known
+                const bool prev = (context[q] & kPrevWord) != 0;
+                nfa.closure(from, (context[q] & kAtStart) != 0, false, prev != w ? Nfa::kBoundary : Nfa::kNoBoundary);
+                matched = nfa.has_match(from);
+            }
             std::vector<int> mv;
-            for (int s : sets[q]) {
+            for (int s : from) {
                 const NState& n = nfa.st[s];
                 if (n.t == NState::SET && nfa.sets[n.set_id].test(rep[c])) mv.push_back(n.out);
             }
             nfa.closure(mv, false, false);
             std::vector<int> u;
             std::set_union(mv.begin(), mv.end(), inject.begin(), inject.end(), std::back_inserter(u));
-            const int to = intern(u);
+            if (matched && !std::binary_search(u.begin(), u.end(), match)) {   // ACCEPT on this byte
+                u.push_back(match);
+                std::sort(u.begin(), u.end());
+            }
+            const int to = intern(u, wa && w ? kPrevWord : 0);
             if (d.next.size() < (q + 1) * (size_t)d.n_classes) d.next.resize((q + 1) * (size_t)d.n_classes);
-            d.next[q * d.n_classes + c] = (uint8_t)to;
+            d.next[q * d.n_classes + c] = (uint16_t)to;
         }
     }
     const int S = (int)sets.size();
@@ -536,12 +646,14 @@ Dfa build_dfa(const std::string& pattern) {
     for (int q = 0; q < S; ++q) {
         if (nfa.has_match(sets[q])) d.acc[q] |= 1;
         std::vector<int> e = sets[q];
-        nfa.closure(e, false, true);
+        // the end of the input counts as a non-word neighbour
+        const int wb = !wa ? Nfa::kPending : (context[q] & kPrevWord) ? Nfa::kBoundary : Nfa::kNoBoundary;
+        nfa.closure(e, (context[q] & kAtStart) != 0, true, wb);
         if (nfa.has_match(e)) d.acc[q] |= 2;
     }
     {
         std::vector<int> e = init;
-        nfa.closure(e, true, true);
+        nfa.closure(e, true, true, wa ? Nfa::kNoBoundary : Nfa::kPending);   // empty input: non-word both sides
         if (nfa.has_match(e)) d.acc[d.init] |= 8;
     }
     // states from which no match can complete: stop early with false
@@ -564,20 +676,26 @@ Dfa build_dfa(const std::string& pattern) {
 struct Packed {
     int K = 0, C = 0, init = 0, empty = 0, P = 0;
     std::vector<uint8_t> endacc, cls, next, clsp, pair;
+    bool wide = false;              // the wide blob: next16 instead of next, no pair table
+    std::vector<uint16_t> next16;
 };
 
 constexpr int kPairTableMax = 4096;       // K * P * P bytes: the two-byte table is optional
 
 constexpr int kByteTableMaxStates = 32;   // K * 256 <= 8 KiB: index by the byte, skip cls[]
 
-Packed pack(const Dfa& d, bool pairs) {
+constexpr uint32_t kWideHeader = 12;
+
+uint32_t blob_size(const Packed& p);
+
+Packed pack(const Dfa& d, bool pairs, bool extended) {
     const int S = (int)d.acc.size();
     // live = neither "match complete" (absorbing true) nor "no match possible"
     std::vector<int> id(S, -1);
     int K = 0;
     for (int q = 0; q < S; ++q)
         if (!(d.acc[q] & 1) && !(d.acc[q] & 4)) id[q] = K++;
-    if (K + 2 > 256) throw Unsupported{};
+    if (K + 2 > 256 && !extended) throw Unsupported{};
     auto map = [&](int q) { return (d.acc[q] & 1) ? K : (d.acc[q] & 4) ? K + 1 : id[q]; };
     Packed p;
     p.K = K;
@@ -586,6 +704,19 @@ Packed pack(const Dfa& d, bool pairs) {
     p.endacc.assign(K, 0);
     for (int q = 0; q < S; ++q)
         if (id[q] >= 0) p.endacc[id[q]] = (d.acc[q] >> 1) & 1;
+    if (K + 2 > 256) {   // 16-bit state ids, through the byte classes
+        p.wide = true;
+        p.C = d.n_classes;
+        p.cls.assign(d.cls, d.cls + 256);
+        p.next16.assign((size_t)K * p.C, 0);
+        for (int q = 0; q < S; ++q) {
+            if (id[q] < 0) continue;
+            for (int c = 0; c < p.C; ++c)
+                p.next16[(size_t)id[q] * p.C + c] = (uint16_t)map(d.next[(size_t)q * d.n_classes + c]);
+        }
+        if (blob_size(p) > kWideBlobMax) throw Unsupported{};   // no block's LDS pool holds it
+        return p;
+    }
     const bool bytes = K <= kByteTableMaxStates;
     p.C = bytes ? 256 : d.n_classes;
     if (!bytes) p.cls.assign(d.cls, d.cls + 256);
@@ -617,6 +748,7 @@ Packed pack(const Dfa& d, bool pairs) {
 }
 
 uint32_t blob_size(const Packed& p) {
+    if (p.wide) return kWideHeader + 256 + ((p.K + 3) & ~3) + 2u * (uint32_t)p.K * p.C;
     uint32_t n = 8 + ((p.K + 3) & ~3) + (p.C == 256 ? 0 : 256) + (uint32_t)p.K * p.C;
     if (p.P) n = ((n + 3) & ~3u) + 256 + (uint32_t)p.K * p.P * p.P;
     return n;
@@ -695,6 +827,7 @@ struct Bitpar {
             it.k = n.t == Node::BOL ? Item::BOL : Item::EOL;
             return {{it}};
         }
+        case Node::WORDB: case Node::NWORDB: throw Unsupported{};   // \b \B: the DFA's
         case Node::CAT: {
             Seqs r{{}};
             for (int k : n.kids) r = product(r, expand(k));
@@ -755,8 +888,8 @@ struct BitparBlob {
     uint64_t B[256] = {};
 };
 
-BitparBlob build_bitpar(const std::string& pattern) {
-    Parser ps(pattern);
+BitparBlob build_bitpar(const std::string& pattern, bool extended) {
+    Parser ps(pattern, extended);
     const int root = ps.parse();
     Bitpar bp(ps.nodes);
     const Seqs all = bp.expand(root);
@@ -892,6 +1025,24 @@ int bitpar_search(const uint8_t* p, const uint8_t* s, uint32_t n) {
     return (D & Fe) != 0;
 }
 
+// The host executor of a wide blob: the kernel's walk.
+int wide_search(const uint8_t* p, const uint8_t* s, uint32_t n) {
+    uint16_t h[4];
+    std::memcpy(h, p, 8);
+    const uint32_t C = h[1], K = h[2];
+    const uint8_t* cls = p + kWideHeader;
+    const uint8_t* endacc = cls + 256;
+    const uint8_t* next = endacc + ((K + 3) & ~3u);   // u16 entries, 4-B aligned in the blob
+    if (n == 0) return p[8];
+    uint32_t q = h[3];
+    for (uint32_t i = 0; i < n && q < K; ++i) {
+        uint16_t t;
+        std::memcpy(&t, next + 2 * ((size_t)q * C + cls[s[i]]), 2);
+        q = t;
+    }
+    return q >= K ? q == K : endacc[q];
+}
+
 }  // namespace
 
 extern "C" {
@@ -908,9 +1059,10 @@ int bt_payload_dfa_compile_ex(const char* expression, uint32_t flags, void* blob
     } catch (const std::regex_error&) {
         return BT_E_INVALID_ARGUMENT;
     }
+    const bool extended = (flags & BT_DFA_EXTENDED) != 0;
     if (!(flags & BT_DFA_NO_BITPAR)) {   // the bit-parallel form where the pattern fits it
         try {
-            const BitparBlob o = build_bitpar(e);
+            const BitparBlob o = build_bitpar(e, extended);
             *size = bitpar_size(o);
             if (!blob) return BT_OK;
             if (cap < *size) return BT_E_RESOURCE;
@@ -921,7 +1073,7 @@ int bt_payload_dfa_compile_ex(const char* expression, uint32_t flags, void* blob
     }
     Packed pk;
     try {
-        pk = pack(build_dfa(e), !(flags & BT_DFA_NO_PAIRS));
+        pk = pack(build_dfa(e, extended), !(flags & BT_DFA_NO_PAIRS), extended);
     } catch (const Unsupported&) {
         return BT_E_NOT_IMPLEMENTED;
     }
@@ -930,6 +1082,15 @@ int bt_payload_dfa_compile_ex(const char* expression, uint32_t flags, void* blob
     if (cap < *size) return BT_E_RESOURCE;
     uint8_t* p = static_cast<uint8_t*>(blob);
     std::memset(p, 0, *size);
+    if (pk.wide) {
+        const uint16_t h[4] = {kWideMagic, (uint16_t)pk.C, (uint16_t)pk.K, (uint16_t)pk.init};
+        std::memcpy(p, h, 8);
+        p[8] = (uint8_t)pk.empty;
+        std::memcpy(p + kWideHeader, pk.cls.data(), 256);
+        std::memcpy(p + kWideHeader + 256, pk.endacc.data(), pk.K);
+        std::memcpy(p + kWideHeader + 256 + ((pk.K + 3) & ~3), pk.next16.data(), 2 * pk.next16.size());
+        return BT_OK;
+    }
     const uint16_t k16 = (uint16_t)pk.K, c16 = (uint16_t)pk.C;
     std::memcpy(p, &k16, 2);
     std::memcpy(p + 2, &c16, 2);
@@ -959,6 +1120,7 @@ int bt_payload_dfa_search(const void* blob, const uint8_t* s, uint32_t n) {
     uint16_t K, C;
     std::memcpy(&K, p, 2);
     if (K == kBitparMagic) return bitpar_search(p, s, n);
+    if (K == kWideMagic) return wide_search(p, s, n);
     std::memcpy(&C, p + 2, 2);
     const uint8_t* endacc = p + 8;
     const uint8_t* cls = endacc + ((K + 3) & ~3);

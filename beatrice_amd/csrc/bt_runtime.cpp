@@ -903,8 +903,10 @@ int compile_program(const bt_filter_desc* f, uint32_t n, uint32_t ctx_flags, Com
             // the compiler's preferred form (bit-parallel where it fits, else the DFA with its
             // two-byte table); when that does not fit the pool, the DFA, then the DFA without
             // the optional table
-            const uint32_t base = (ctx_flags & BT_OPT_PAYLOAD_DFA) ? BT_DFA_NO_BITPAR : 0u;
-            const uint32_t forms[3] = {base, BT_DFA_NO_BITPAR, BT_DFA_NO_BITPAR | BT_DFA_NO_PAIRS};
+            // the wider subset (\b \B, POSIX classes, wide DFAs) in every form tried, where asked for
+            const uint32_t ext = (ctx_flags & BT_OPT_PAYLOAD_EXTENDED) ? BT_DFA_EXTENDED : 0u;
+            const uint32_t base = ((ctx_flags & BT_OPT_PAYLOAD_DFA) ? BT_DFA_NO_BITPAR : 0u) | ext;
+            const uint32_t forms[3] = {base, BT_DFA_NO_BITPAR | ext, BT_DFA_NO_BITPAR | BT_DFA_NO_PAIRS | ext};
             const size_t at = (pool.size() + 15) & ~(size_t)15;
             uint32_t size = 0, fl = 0;
             bool fits = false;

@@ -314,6 +314,11 @@ typedef struct bt_opts {
                                       instead of bytes 12..43 (A/B only) */
 #define BT_OPT_PAYLOAD_DFA 0x40000u /* PAYLOAD slots as byte DFAs even where the bit-parallel
                                       form fits (A/B only) */
+#define BT_OPT_PAYLOAD_EXTENDED 0x80000u /* PAYLOAD slots: also compile \b \B, POSIX bracket
+                                      classes ([[:alpha:]]) and DFAs of up to 4,096 states for
+                                      the GPU (BT_DFA_EXTENDED) instead of leaving them on the
+                                      host; contexts and groups (opt-in: the default
+                                      classification is unchanged) */
 
 /* descriptor formats (bt_batch.desc_format) */
 #define BT_DESC_PACKED 0u          /* bt_pkt_desc: u64 offset:48 | length:16            */
@@ -447,7 +452,10 @@ int  bt_host_unregister(bt_ctx* ctx, void* host);
  * PacketFilter::applyPayloadFilter (src/PacketFilter.cpp:288-321) for the regular
  * subset of libstdc++'s ECMAScript grammar: bt_filter_compile compiles every PAYLOAD
  * expression it can once (BT_K_PAYLOAD slots, up to 16 KiB of tables per program); the
- * rest stay BT_K_HOST. The compiler itself is in include/beatrice_gpu_bench.h.
+ * rest stay BT_K_HOST: backreferences, lookaheads, \c \u, and by default also \b \B,
+ * POSIX bracket classes and DFAs of more than 254 live states, which a context created
+ * with BT_OPT_PAYLOAD_EXTENDED compiles for the GPU as well. The compiler itself is in
+ * include/beatrice_gpu_bench.h.
  *   bt_payload_dfa_eval  applyPayloadFilter(frame, len) on the host with a compiled slot's
  *                        blob (bt_filter_dfa_pool): the C++ filter's continuation of a
  *                        chain the device handed over */

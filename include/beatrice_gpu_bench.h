@@ -96,7 +96,9 @@ int  bt_filter_compile_host(const bt_filter_desc* filters, uint32_t n,
  * subset of libstdc++'s ECMAScript grammar: the expression is compiled once to a byte
  * DFA that the kernel runs over the same <= 100-byte window after the IPv4 header.
  * bt_filter_compile does this for every PAYLOAD filter it can (BT_K_PAYLOAD slots, up
- * to 16 KiB of tables per program); the rest stay BT_K_HOST. The helpers below expose
+ * to 16 KiB of tables per program); the rest stay BT_K_HOST. By default \b \B, POSIX
+ * bracket classes and DFAs of more than 254 live states are among the rest;
+ * BT_DFA_EXTENDED below (BT_OPT_PAYLOAD_EXTENDED on a context) takes them too. The helpers below expose
  * the compiler and a host executor of the same DFA (tests, other hosts).
  *   bt_payload_dfa_compile  BT_OK (+ blob; blob == NULL: size only),
  *                           BT_E_INVALID_ARGUMENT if std::regex rejects the expression
@@ -113,6 +115,14 @@ int  bt_payload_dfa_compile(const char* expression, void* blob, uint32_t cap, ui
 /* BT_DFA_NO_BITPAR: always the DFA, never the bit-parallel form the compiler prefers for
  * unions of linear class sequences (A/B and tests; blob layouts in bt_regex_dfa.cpp). */
 #define BT_DFA_NO_BITPAR 0x2u
+/* BT_DFA_EXTENDED: the wider subset — \b and \B (one bit of previous-byte word class in the
+ * DFA state), POSIX classes inside brackets ([[:alpha:]] .. [[:xdigit:]], [[:d:]] [[:w:]]
+ * [[:s:]]; C locale) and DFAs of up to 4,096 states (more than 254 live states: the wide
+ * blob with 16-bit state ids, when it fits 16 KiB). Backreferences, lookaheads, \c \u,
+ * [[.x.]] and [[=x=]] still return BT_E_NOT_IMPLEMENTED. A pattern the default subset takes
+ * compiles to the same bytes with the flag. bt_filter_compile sets it for contexts created
+ * with BT_OPT_PAYLOAD_EXTENDED. */
+#define BT_DFA_EXTENDED 0x4u
 int  bt_payload_dfa_compile_ex(const char* expression, uint32_t flags, void* blob, uint32_t cap, uint32_t* size);
 int  bt_payload_dfa_search(const void* blob, const uint8_t* s, uint32_t n);
 /* The same walk, and each frame's header prefix is also copied into slot i of `slots`
