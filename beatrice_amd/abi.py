@@ -186,7 +186,7 @@ EXPORTS = [
     "bt_payload_dfa_compile", "bt_payload_dfa_compile_ex", "bt_payload_dfa_search", "bt_payload_dfa_eval",
     "bt_format_records", "bt_format_records_to",
     "bt_record_unpack", "bt_record_slabs", "bt_ring_gather_tpv3", "bt_ring_gather_dense_tpv3",
-    "bt_ring_gather_lean_tpv3", "bt_ring_stage_tpv3",
+    "bt_ring_gather_lean_tpv3", "bt_ring_stage_tpv3", "bt_ring_stage_tpv3_ex", "bt_filter_resume_device",
     "bt_group_create", "bt_group_destroy", "bt_group_size", "bt_group_member", "bt_group_filter_compile",
     "bt_group_parse_filter", "bt_group_parse_filter_ptrs", "bt_group_split",
     "bt_group_split_cost", "bt_group_cost", "bt_group_thread_budget", "bt_group_host_register",
@@ -222,6 +222,7 @@ def lib() -> ctypes.CDLL:
                                                   u32, ctypes.POINTER(u32)]),
         "bt_reserve": (ctypes.c_int, [vp, u32]),
         "bt_parse_filter_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp]),
+        "bt_filter_resume_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
                                                         vp]),
         "bt_parse_filter": (ctypes.c_int, [vp, vp, vp, u32, vp, vp, vp, vp, vp]),
@@ -267,6 +268,9 @@ def lib() -> ctypes.CDLL:
                                                      ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "bt_ring_stage_tpv3": (ctypes.c_int, [vp, ctypes.POINTER(Tpv3Ring), u32, u32, ctypes.POINTER(RingStageOpts),
                                               vp, vp, vp, vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "bt_ring_stage_tpv3_ex": (ctypes.c_int, [vp, ctypes.POINTER(Tpv3Ring), u32, u32, ctypes.POINTER(RingStageOpts),
+                                                 u32, vp, vp, vp, vp, vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32),
+                                                 ctypes.POINTER(u32)]),
         "bt_payload_dfa_compile": (ctypes.c_int, [ctypes.c_char_p, vp, u32, ctypes.POINTER(u32)]),
         "bt_payload_dfa_compile_ex": (ctypes.c_int, [ctypes.c_char_p, u32, vp, u32, ctypes.POINTER(u32)]),
         "bt_payload_dfa_search": (ctypes.c_int, [vp, vp, u32]),
@@ -503,6 +507,13 @@ class Context:
 
     def run_device(self, batch: Batch, outs: Outputs, stream=None):
         _check(lib().bt_parse_filter_device(self.h, ctypes.byref(batch), ctypes.byref(outs), stream))
+
+    def resume_device(self, batch: Batch, outs: Outputs, stream=None):
+        """bt_filter_resume_device: the second pass over a batch first run with BATCH_PREFIXES.
+        `batch` holds the whole frames of the same packets (flags 0), outs.decide the first
+        pass's decision bytes (rewritten in place); outs.verdict / pass_idx / n_pass, when set,
+        are rebuilt from the final bytes. outs.records must be None."""
+        _check(lib().bt_filter_resume_device(self.h, ctypes.byref(batch), ctypes.byref(outs), stream))
 
     def run_device_async(self, batch: Batch, outs: Outputs, stream=None, done_event=None):
         """bt_parse_filter_device_async: the compaction on the context's compaction stream;
@@ -803,27 +814,43 @@ def ring_gather_tpv3(ring: np.ndarray, block_size: int, n_blocks: int, slots: np
     return out[slot_base:slot_base + nd.value], nb.value
 
 
+RING_RESUME_PAYLOAD = 0x1
+
+
 def ring_stage_tpv3(ctx: "Context", ring: np.ndarray, block_size: int, n_blocks: int, desc: np.ndarray,
                     decide: np.ndarray, verdict: np.ndarray | None = None, slots: np.ndarray | None = None,
                     first: int = 0, count: int | None = None, batch_blocks: int = 0, gather: bool = False,
-                    in_place_every: int = 0, in_place_blocks: int = 0):
+                    in_place_every: int = 0, in_place_blocks: int = 0, resume_payload: bool = False,
+                    ring_desc: np.ndarray | None = None, want_host: bool = False):
     """bt_ring_stage_tpv3: blocks [first, first + count) of a registered ring through the
     context's filter, walk of each batch overlapping the kernels of the one before. desc /
     decide (/ verdict, slots) are host arrays registered with ctx (abi.host_array + register).
-    Returns (frames, passed)."""
+    Returns (frames, passed).
+    resume_payload / ring_desc / want_host: bt_ring_stage_tpv3_ex. resume_payload=True is
+    BT_RING_RESUME_PAYLOAD (gathered batches of a program with a GPU PAYLOAD slot are finished by
+    the resume kernel; ring_desc: registered uint64 array as long as desc, for the frames' ring
+    descriptors). want_host=True returns (frames, passed, n_host), n_host = the frames whose final
+    code is still DECIDE_HOST."""
     cap = min(len(desc), len(decide))
     if verdict is not None and len(verdict) * 64 < cap:
         raise ValueError("verdict: need ceil(cap / 64) words")
     if slots is not None and slots.nbytes < cap * PREFIX_SLOT:
         raise ValueError("slots: need cap * PREFIX_SLOT bytes")
+    if ring_desc is not None and (ring_desc.dtype != np.uint64 or len(ring_desc) < cap):
+        raise ValueError("ring_desc: uint64, at least as long as desc")
     r = Tpv3Ring(ring.ctypes.data, block_size, n_blocks, 0)
     o = RingStageOpts(batch_blocks, 2 if gather == "adaptive" else int(bool(gather)), in_place_every, in_place_blocks)
-    nd, npass = ctypes.c_uint32(), ctypes.c_uint32()
-    _check(lib().bt_ring_stage_tpv3(ctx.h, ctypes.byref(r), first, n_blocks if count is None else count, ctypes.byref(o),
-                                    desc.ctypes.data, None if slots is None else slots.ctypes.data,
-                                    decide.ctypes.data, None if verdict is None else verdict.ctypes.data, cap,
-                                    ctypes.byref(nd), ctypes.byref(npass)))
-    return nd.value, npass.value
+    nd, npass, nhost = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    head = (ctx.h, ctypes.byref(r), first, n_blocks if count is None else count, ctypes.byref(o))
+    tail = (None if slots is None else slots.ctypes.data, decide.ctypes.data,
+            None if verdict is None else verdict.ctypes.data, cap, ctypes.byref(nd), ctypes.byref(npass))
+    if not (resume_payload or ring_desc is not None or want_host):
+        _check(lib().bt_ring_stage_tpv3(*head, desc.ctypes.data, *tail))
+        return nd.value, npass.value
+    _check(lib().bt_ring_stage_tpv3_ex(*head, RING_RESUME_PAYLOAD if resume_payload else 0, desc.ctypes.data,
+                                       None if ring_desc is None else ring_desc.ctypes.data, *tail,
+                                       ctypes.byref(nhost)))
+    return (nd.value, npass.value, nhost.value) if want_host else (nd.value, npass.value)
 
 
 def ring_walk_tpv3_gpu(ctx: "Context", ring: np.ndarray, ring_dev: int, block_size: int, n_blocks: int,

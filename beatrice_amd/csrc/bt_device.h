@@ -89,6 +89,28 @@ int launch_compact(const uint64_t* verdict, uint32_t n, uint32_t* chunk_sums, ui
                    uint32_t* n_pass, void* stream);
 int device_grid_blocks(int device);
 
+// ---- second pass of the PAYLOAD filter over a prefix batch (bt_payload_resume.hip) ----
+// One batch of n WHOLE frames (base / desc / stride / bytes as in MainArgs) and the first pass's
+// decision bytes, rewritten in place where the code is BT_DECIDE_HOST at a BT_K_PAYLOAD slot.
+struct ResumeArgs {
+    const uint8_t* base;
+    const uint64_t* desc;      // nullptr: fixed stride
+    uint32_t desc_words;       // 1 packed, 2 xdp_desc
+    uint64_t bytes;            // read limit from base (read_limit)
+    uint32_t stride;
+    uint32_t n;
+    uint32_t ntiles;           // ceil(n / 64): the scan's unit
+    uint8_t* decide;           // n bytes, read and written
+    const uint8_t* dfa;        // PAYLOAD DFA pool (device), copied to dynamic LDS per block
+    uint32_t dfa_bytes;        // 0: no BT_K_PAYLOAD slot, nothing to do
+};
+// Asynchronous on `stream`; nothing is launched when n == 0 or the program has no PAYLOAD slot.
+int launch_payload_resume(const ResumeArgs& a, const DevProgram& prog, void* stream, void* timing_start = nullptr,
+                          void* timing_stop = nullptr);
+// verdict[j] bit i = (decide[64 j + i] >> 6) == BT_DECIDE_PASS, all ceil(n / 64) words.
+int launch_verdict_words(const uint8_t* decide, uint32_t n, uint64_t* verdict, void* stream);
+uint32_t bounds_take_resume(void* stream, BoundsLog* first);
+
 // The limit the kernels' 16-B chunk reads are checked against: chunks sit at 16-B offsets
 // from base, and a chunk may pass the buffer's last byte, but never the end of the
 // 16-B-aligned (absolute address) granule that holds it, so never another page.

@@ -26,6 +26,7 @@
 
 #include "beatrice_gpu_bench.h"
 #include "bt_device.h"
+#include "bt_resume_host.h"
 #include "bt_hip_util.h"
 #include "bt_host_pool.h"
 #include "bt_host.h"
@@ -416,6 +417,7 @@ int check_bounds(hipStream_t st, hipStream_t cst, const char* what) {
     uint32_t k = bounds_take_main(st, &f);
     if (!k && cst && cst != st) k = bounds_take_main(cst, &f);
     if (!k) k = bounds_take_extract(st, &f);
+    if (!k) k = bounds_take_resume(st, &f);
     if (k) {
         fprintf(stderr, "BT_DEBUG_BOUNDS: %s: %u failed checks, first %s (site %u) block %u thread %u index %llu "
                 "limit %llu\n", what, k, bounds_site_name(f.site), f.site, f.block, f.lane,
@@ -428,6 +430,22 @@ int check_bounds(hipStream_t st, hipStream_t cst, const char* what) {
     (void)cst;
     (void)what;
 #endif
+    return BT_OK;
+}
+
+// A launch on `st` reads the context's current DFA pool: the pool stays untouched until it has
+// run (a recompile that reuses the buffer waits for every reader's event).
+int dfa_read_on(bt_ctx* c, hipStream_t st) {
+    auto& rd = c->dfa_readers[c->dfa_cur];
+    auto it = std::find_if(rd.begin(), rd.end(), [st](const auto& x) { return x.first == st; });
+    if (it == rd.end()) {
+        hipEvent_t e = nullptr;
+        if (!c->dfa_spare.empty()) { e = c->dfa_spare.back(); c->dfa_spare.pop_back(); }
+        else HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        rd.emplace_back(st, e);
+        it = rd.end() - 1;
+    }
+    HIP_TRY(hipEventRecord(it->second, st));
     return BT_OK;
 }
 
@@ -551,18 +569,7 @@ int run_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, hipStream_t st
     int rc = launch_main(a, c->prog, rec, filter, c->grid, !(c->opts.flags & BT_OPT_NO_PREFETCH), st, e0, mend);
     if (rc) return fail(rc, "main kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     if (w && !o->verdict) { if ((rc = ws_done(c, w, st))) return rc; }
-    if (a.dfa_bytes) {   // the pool this launch reads stays untouched until it has run
-        auto& rd = c->dfa_readers[c->dfa_cur];
-        auto it = std::find_if(rd.begin(), rd.end(), [st](const auto& x) { return x.first == st; });
-        if (it == rd.end()) {
-            hipEvent_t e = nullptr;
-            if (!c->dfa_spare.empty()) { e = c->dfa_spare.back(); c->dfa_spare.pop_back(); }
-            else HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            rd.emplace_back(st, e);
-            it = rd.end() - 1;
-        }
-        HIP_TRY(hipEventRecord(it->second, st));
-    }
+    if (a.dfa_bytes && (rc = dfa_read_on(c, st))) return rc;
     if (compact) {
         if (piped) HIP_TRY(hipStreamWaitEvent(cst, mend, 0));
         if ((rc = ws_touch(c, w, cst))) return rc;
@@ -1007,6 +1014,51 @@ int bt_parse_filter_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, vo
     return run_device(c, b, o, st, false, nullptr, nullptr);
 }
 
+// The second pass over a prefix batch (bt_payload_resume.hip): the resume kernel where the
+// program has a BT_K_PAYLOAD slot, then the verdict words and the pass list from the final bytes.
+int bt_filter_resume_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, void* stream) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (const char* why = resume_args_error(c, b, o)) return fail(BT_E_INVALID_ARGUMENT, "%s", why);
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool compact = o->pass_idx || o->n_pass;
+    if (b->n == 0) {
+        if (o->n_pass) HIP_TRY(hipMemsetAsync(o->n_pass, 0, 4, st));
+        return BT_OK;
+    }
+    ResumeArgs a{};
+    a.base = b->base;
+    a.desc = static_cast<const uint64_t*>(b->desc);
+    a.desc_words = b->desc_format == BT_DESC_XDP ? 2u : 1u;
+    a.bytes = read_limit(b->base, b->desc || b->bytes ? b->bytes : (uint64_t)b->n * b->stride);
+    a.stride = b->stride;
+    a.n = b->n;
+    a.ntiles = (b->n + 63) / 64;
+    a.decide = o->decide;
+    a.dfa = c->dfa_dev[c->dfa_cur];
+    a.dfa_bytes = (uint32_t)c->dfa_pool.size();
+    int rc = launch_payload_resume(a, c->prog, st);
+    if (rc) return fail(rc, "resume kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (a.dfa_bytes && (rc = dfa_read_on(c, st))) return rc;
+    if (o->verdict || compact) {
+        bt_ctx::Ws* w = nullptr;
+        if (compact) {
+            if ((rc = ensure_ws(c, b->n))) return rc;
+            w = &c->ws[c->ws_next];
+            c->ws_next ^= 1;
+            if ((rc = ws_touch(c, w, st))) return rc;
+        }
+        uint64_t* words = o->verdict ? o->verdict : w->verdict;
+        if ((rc = launch_verdict_words(o->decide, b->n, words, st))) return fail(rc, "verdict kernel launch failed");
+        if (compact) {
+            rc = launch_compact(words, b->n, w->chunk_sums, o->pass_idx, o->n_pass, st);
+            if (rc) return fail(rc, "compaction launch failed");
+            if ((rc = ws_done(c, w, st))) return rc;
+        }
+    }
+    return check_bounds(st, st, "payload resume");
+}
 
 int bt_parse_filter_device_async(bt_ctx* c, const bt_batch* b, const bt_outputs* o, void* stream,
                                  void* done_event) {

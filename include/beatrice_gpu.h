@@ -78,7 +78,9 @@ extern "C" {
 /* ABI history: 1 = round 1-3. 2 = round 4: a descriptor batch must state bt_batch.bytes
  * (0 was "unbounded" before and is now BT_E_INVALID_ARGUMENT); bt_group_host_register /
  * bt_group_parse_filter_mapped / bt_group_split_cost / bt_context_placement added. Hosts
- * built against an older header should check bt_abi_version() >= the version they need. */
+ * built against an older header should check bt_abi_version() >= the version they need.
+ * Added within 2 (new entry points only, nothing existing changed; a host that needs them can
+ * look the symbols up): bt_filter_resume_device, bt_ring_stage_tpv3_ex. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -397,6 +399,23 @@ int  bt_reserve(bt_ctx* ctx, uint32_t n);
  * outputs are produced when any of verdict/decide/pass_idx/n_pass is set. */
 int  bt_parse_filter_device(bt_ctx* ctx, const bt_batch* batch, const bt_outputs* out, void* stream);
 
+/* Second pass for a batch first run with BT_BATCH_PREFIXES: `frames` holds the WHOLE frames of
+ * the same n packets, in the same order (flags must not have BT_BATCH_PREFIXES); out->decide
+ * holds the first pass's n decision bytes and is rewritten in place. out->verdict (optional):
+ * all ceil(n/64) words rebuilt from the final decision bytes; out->pass_idx / n_pass
+ * (optional): the ordered pass list from them. out->records must be NULL. Asynchronous on
+ * `stream` (NULL = the context's stream), after which the outputs equal those of
+ * bt_parse_filter_device over `frames`. A program without a BT_K_PAYLOAD slot: only the
+ * optional verdict / pass list are rebuilt.
+ * The pass takes every decision left as BT_DECIDE_HOST at a BT_K_PAYLOAD slot s (the first pass
+ * could not read the payload), evaluates slots s .. n-1 over the whole frame on the GPU and
+ * rewrites the byte; every other byte, BT_DECIDE_HOST at a BT_K_HOST slot included, is left as
+ * it is. It reads frame bytes 12..37 and the PAYLOAD window, each 16-B chunk under the rule of
+ * bt_parse_filter_device (a chunk past `bytes` reads as zeros). BT_E_INVALID_ARGUMENT: a null
+ * argument, BT_BATCH_PREFIXES / BT_BATCH_LEAN set, records != NULL, decide == NULL, a
+ * descriptor batch with bytes == 0. */
+int  bt_filter_resume_device(bt_ctx* ctx, const bt_batch* frames, const bt_outputs* out, void* stream);
+
 /* Pipelined form for a stream of batches. The main kernel runs on `stream` as above
  * (records, decide and verdict are complete in stream order); the ordered compaction
  * (pass_idx, n_pass) runs on the context's own compaction stream once that kernel has
@@ -542,6 +561,22 @@ typedef struct bt_ring_stage_opts {
 int  bt_ring_stage_tpv3(bt_ctx* ctx, const bt_tpv3_ring* ring, uint32_t first_block, uint32_t n_blocks,
                         const bt_ring_stage_opts* opts, bt_pkt_desc* desc, uint8_t* slots, uint8_t* decide,
                         uint64_t* verdict, uint32_t cap, uint32_t* n_desc, uint32_t* n_pass);
+/* The same with flags and two more arguments; flags = 0 is bt_ring_stage_tpv3 exactly (ring_desc
+ * unused). BT_RING_RESUME_PAYLOAD, the two-pass PAYLOAD path: a gathered batch holds bytes 12..43
+ * of each frame, so its launch leaves BT_DECIDE_HOST at the program's BT_K_PAYLOAD slots; with the
+ * flag, and a program that has such a slot, every gathered batch also gets its frames' ring
+ * descriptors in `ring_desc` (cap entries, registered with the context like desc; NULL while
+ * gathering is BT_E_INVALID_ARGUMENT) and its launch is followed on the same stream by
+ * bt_filter_resume_device over (the ring, ring_desc + the batch's start, its count), so gathered
+ * and in-place batches decide alike. The host walk of the next batch overlaps both kernels;
+ * batches read in place are unchanged. n_host (optional): the frames whose final code is still
+ * BT_DECIDE_HOST (CUSTOM slots and PAYLOAD expressions outside the GPU subset); `verdict` and
+ * `n_pass` treat those frames as not passed, the host continues them from decide. */
+#define BT_RING_RESUME_PAYLOAD 0x1u
+int  bt_ring_stage_tpv3_ex(bt_ctx* ctx, const bt_tpv3_ring* ring, uint32_t first_block, uint32_t n_blocks,
+                           const bt_ring_stage_opts* opts, uint32_t flags, bt_pkt_desc* desc,
+                           bt_pkt_desc* ring_desc, uint8_t* slots, uint8_t* decide, uint64_t* verdict,
+                           uint32_t cap, uint32_t* n_desc, uint32_t* n_pass, uint32_t* n_host);
 
 /* ---- several devices in one process -------------------------------
  * The reference runs one daemon process whose capture threads feed one plugin set
