@@ -102,6 +102,35 @@ class Outputs(ctypes.Structure):
                 ("decide", ctypes.c_void_p), ("pass_idx", ctypes.c_void_p), ("n_pass", ctypes.c_void_p)]
 
 
+class PackOpts(ctypes.Structure):
+    """bt_pack_opts (include/beatrice_gpu.h)."""
+    _fields_ = [("lead", ctypes.c_uint32), ("snap", ctypes.c_uint32), ("align", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class PackOut(ctypes.Structure):
+    """bt_pack_out: device-visible pointers."""
+    _fields_ = [("bytes", ctypes.c_void_p), ("cap", ctypes.c_uint64), ("desc", ctypes.c_void_p),
+                ("total", ctypes.c_void_p), ("n_packed", ctypes.c_void_p)]
+
+
+class PcapInfo(ctypes.Structure):
+    """bt_pcap_info: what bt_pcap_index read from a capture file's global header."""
+    _fields_ = [("magic", ctypes.c_uint32), ("swapped", ctypes.c_uint32), ("nanosecond", ctypes.c_uint32),
+                ("snaplen", ctypes.c_uint32), ("linktype", ctypes.c_uint32), ("truncated", ctypes.c_uint32),
+                ("end", ctypes.c_uint64)]
+
+
+class PcapResult(ctypes.Structure):
+    """bt_pcap_result: bt_pcap_filter's counts."""
+    _fields_ = [("n_in", ctypes.c_uint64), ("n_pass", ctypes.c_uint64), ("n_reject", ctypes.c_uint64),
+                ("n_throw", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("truncated", ctypes.c_uint32),
+                ("chunks", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class Timing(ctypes.Structure):
     """bt_timing (include/beatrice_gpu.h): bt_time_device_ex's breakdown."""
     _fields_ = [("span_ms", ctypes.c_float), ("main_ms", ctypes.c_float), ("main_min_ms", ctypes.c_float),
@@ -192,7 +221,8 @@ EXPORTS = [
     "bt_group_split_cost", "bt_group_cost", "bt_group_thread_budget", "bt_group_host_register",
     "bt_group_host_unregister", "bt_group_parse_filter_mapped", "bt_context_placement", "bt_node_cpus",
     "bt_usable_cpus", "bt_extract_host", "bt_filter_dfa_pool", "bt_group_split_plan",
-    "bt_group_host_parallel",
+    "bt_group_host_parallel", "bt_pass_pack_device", "bt_pcap_index", "bt_pcap_filter", "bt_time_pass_pack",
+    "bt_time_copy_d2d",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -223,6 +253,13 @@ def lib() -> ctypes.CDLL:
         "bt_reserve": (ctypes.c_int, [vp, u32]),
         "bt_parse_filter_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp]),
         "bt_filter_resume_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp]),
+        "bt_pass_pack_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(PackOpts),
+                                               ctypes.POINTER(PackOut), vp]),
+        "bt_time_pass_pack": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(PackOpts),
+                                             ctypes.POINTER(PackOut), u32, vp]),
+        "bt_time_copy_d2d": (ctypes.c_int, [vp, vp, vp, u64, u32, vp]),
+        "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
+        "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
                                                         vp]),
         "bt_parse_filter": (ctypes.c_int, [vp, vp, vp, u32, vp, vp, vp, vp, vp]),
@@ -344,6 +381,30 @@ def compile_host(filters):
     return [out[i] for i in range(n.value)]
 
 
+def _byte_view(buf) -> np.ndarray:
+    """A contiguous uint8 view (or copy) of bytes / bytearray / a numpy array."""
+    if isinstance(buf, np.ndarray):
+        return np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    return np.frombuffer(buf, np.uint8)
+
+
+def pcap_index(buf, count_only: bool = False):
+    """bt_pcap_index (host only) over a classic pcap file held in memory: (info dict, descriptors)
+    with desc[i] = offset of record i's data | incl_len << 48, up to the last whole record
+    (info["truncated"] = 1 when bytes follow it). count_only: (info, n) without descriptors."""
+    a = _byte_view(buf)
+    keep = a if len(a) else np.zeros(1, np.uint8)
+    info, n = PcapInfo(), ctypes.c_uint64(0)
+    _check(lib().bt_pcap_index(keep.ctypes.data, len(a), ctypes.byref(info), None, 0, ctypes.byref(n)))
+    d = {k: int(getattr(info, k)) for k, _ in info._fields_}
+    if count_only:
+        return d, int(n.value)
+    desc = np.zeros(max(1, n.value), np.uint64)
+    _check(lib().bt_pcap_index(keep.ctypes.data, len(a), ctypes.byref(info), desc.ctypes.data, n.value,
+                               ctypes.byref(n)))
+    return d, desc[:n.value]
+
+
 FMT_JSON, FMT_XML, FMT_CSV, FMT_HUMAN = range(4)
 
 
@@ -428,10 +489,11 @@ class Context:
     """One bt_ctx on one device."""
 
     def __init__(self, device: int = 0, host_chunk_packets: int = 0, grid_waves: int = 0, flags: int = 0,
-                 host_threads: int = 0):
+                 host_threads: int = 0, host_chunk_bytes: int = 0):
         opts = Opts()
         opts.host_threads = host_threads
         opts.host_chunk_packets = host_chunk_packets
+        opts.host_chunk_bytes = host_chunk_bytes
         opts.grid_waves = grid_waves
         opts.flags = flags
         h = ctypes.c_void_p(0)
@@ -514,6 +576,31 @@ class Context:
         pass's decision bytes (rewritten in place); outs.verdict / pass_idx / n_pass, when set,
         are rebuilt from the final bytes. outs.records must be None."""
         _check(lib().bt_filter_resume_device(self.h, ctypes.byref(batch), ctypes.byref(outs), stream))
+
+    def pass_pack(self, batch: Batch, select_dev, out_bytes, cap: int, total, n_packed, desc=None, lead: int = 0,
+                  snap: int = 0, align: int = 1, stream=None):
+        """bt_pass_pack_device: the frames of `batch` whose bit is set in the verdict-layout words
+        at `select_dev`, packed in packet order into out_bytes[:cap]; record k = lead bytes in
+        front of the frame + min(len, snap or len) frame bytes, its slot rounded up to align.
+        Every pointer argument is a device-visible address (int or DeviceBuffer); total (u64) and
+        n_packed (u32) receive the bytes the selection needs and the records that fit; desc
+        (optional) one descriptor per selected packet. Asynchronous on `stream`."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        po = PackOpts(lead, snap, align, 0)
+        out = PackOut(ptr(out_bytes), cap, ptr(desc), ptr(total), ptr(n_packed))
+        _check(lib().bt_pass_pack_device(self.h, ctypes.byref(batch), ptr(select_dev), ctypes.byref(po),
+                                         ctypes.byref(out), stream))
+
+    def pcap_filter(self, buf):
+        """bt_pcap_filter: the classic pcap file in `buf` through the compiled program. Returns
+        (the output pcap as bytes: the input's global header and every passing record, verbatim
+        and in order; the result counts as a dict)."""
+        a = _byte_view(buf)
+        res = PcapResult()
+        _check(lib().bt_pcap_filter(self.h, a.ctypes.data if len(a) else None, len(a), None, 0, ctypes.byref(res)))
+        out = np.empty(max(1, res.out_bytes), np.uint8)
+        _check(lib().bt_pcap_filter(self.h, a.ctypes.data, len(a), out.ctypes.data, res.out_bytes, ctypes.byref(res)))
+        return out[:res.out_bytes].tobytes(), res.as_dict()
 
     def run_device_async(self, batch: Batch, outs: Outputs, stream=None, done_event=None):
         """bt_parse_filter_device_async: the compaction on the context's compaction stream;

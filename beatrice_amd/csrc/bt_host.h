@@ -23,6 +23,13 @@ int compile_program(const bt_filter_desc* f, uint32_t n, uint32_t ctx_flags, Com
 int install_program(bt_ctx* c, const CompiledProgram& p);
 uint32_t ctx_flags(const bt_ctx* c);
 int ctx_device(const bt_ctx* c);
+// The options the context was created with.
+bt_opts ctx_opts(const bt_ctx* c);
+// bt_pcap_filter's staging buffers and streams, kept on the context between calls (bt_pcap.cpp
+// allocates and sizes them; bt_destroy releases them through pcap_stage_free).
+struct PcapStage;
+PcapStage*& ctx_pcap_stage(bt_ctx* c);
+void pcap_stage_free(PcapStage* s);
 // Whether the context's stream still has queued work (hipStreamQuery: not ready).
 bool ctx_stream_busy(bt_ctx* c);
 // The CPUs the context's pool workers are pinned to (its device's NUMA node), or NULL.

@@ -26,6 +26,7 @@
 
 #include "beatrice_gpu_bench.h"
 #include "bt_device.h"
+#include "bt_pack.h"
 #include "bt_resume_host.h"
 #include "bt_hip_util.h"
 #include "bt_host_pool.h"
@@ -117,6 +118,7 @@ struct bt_ctx {
     struct Ws {
         uint32_t* chunk_sums = nullptr;
         uint64_t* verdict = nullptr;
+        PackChunkSum* pack_sums = nullptr;   // bt_pass_pack_device: chunk sums, then a word per tile
         hipStream_t last = nullptr;
         bool lazy = false;             // sync not recorded yet (last is a context stream)
         hipEvent_t sync = nullptr;
@@ -185,6 +187,9 @@ struct bt_ctx {
     uint8_t* ex_h = nullptr;
     uint8_t* ex_d = nullptr;
     size_t ex_cap = 0;
+
+    // bt_pcap_filter's staging (bt_pcap.cpp owns it; pcap_stage_free releases it)
+    bt::PcapStage* pcap = nullptr;
 };
 
 namespace bt {
@@ -339,6 +344,8 @@ void free_ws(bt_ctx* c) {
     for (auto& w : c->ws) {
         if (w.chunk_sums) (void)hipFree(w.chunk_sums);
         if (w.verdict) (void)hipFree(w.verdict);
+        if (w.pack_sums) (void)hipFree(w.pack_sums);
+        w.pack_sums = nullptr;
         w.chunk_sums = nullptr; w.verdict = nullptr; w.last = nullptr; w.lazy = false;
     }
     c->ws_cap = 0;
@@ -357,6 +364,7 @@ int ensure_ws(bt_ctx* c, uint32_t n) {
         if (!w.sync) HIP_TRY(hipEventCreateWithFlags(&w.sync, hipEventDisableTiming));
         HIP_TRY(hipMalloc(&w.chunk_sums, (size_t)nchunks * 4));
         HIP_TRY(hipMalloc(&w.verdict, (size_t)ntiles * 8));
+        HIP_TRY(hipMalloc(&w.pack_sums, (size_t)nchunks * sizeof(PackChunkSum) + (size_t)ntiles * 4));
     }
     for (auto& e : c->main_done)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -846,6 +854,7 @@ void bt_destroy(bt_ctx* c) {
         (void)bt::pin_release(reinterpret_cast<const void*>(r.first), r.second);
     c->host_regs.clear();
     free_host(c);
+    if (c->pcap) { bt::pcap_stage_free(c->pcap); c->pcap = nullptr; }
     c->pool.reset();
     if (c->tgraph) (void)hipGraphExecDestroy(c->tgraph);
     free_ws(c);
@@ -965,6 +974,9 @@ int install_program(bt_ctx* c, const CompiledProgram& p) {
 uint32_t ctx_flags(const bt_ctx* c) { return c->opts.flags; }
 int ctx_device(const bt_ctx* c) { return c->device; }
 
+bt_opts ctx_opts(const bt_ctx* c) { return c->opts; }
+PcapStage*& ctx_pcap_stage(bt_ctx* c) { return c->pcap; }
+
 bool ctx_stream_busy(bt_ctx* c) {
     const bt::DeviceRestore keep_device;
     if (hipSetDevice(c->device) != hipSuccess) return false;
@@ -1060,6 +1072,74 @@ int bt_filter_resume_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, v
     return check_bounds(st, st, "payload resume");
 }
 
+// The ordered pack of the selected frames (bt_pack.hip). e0 / e1: timing events recorded by
+// the first / second kernel's own dispatch (bt_time_pass_pack).
+static int run_pass_pack(bt_ctx* c, const bt_batch* b, const uint64_t* select, const bt_pack_opts* po,
+                         const bt_pack_out* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    if (!c || !b || !select || !po || !out || !out->total || !out->n_packed)
+        return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!out->bytes && out->cap) return fail(BT_E_INVALID_ARGUMENT, "null output with cap %llu", (unsigned long long)out->cap);
+    if (b->flags & (BT_BATCH_PREFIXES | BT_BATCH_LEAN))
+        return fail(BT_E_INVALID_ARGUMENT, "a BT_BATCH_PREFIXES / BT_BATCH_LEAN batch holds no whole frames to pack");
+    if (po->lead > kPackLeadMax) return fail(BT_E_INVALID_ARGUMENT, "lead %u > %u", po->lead, kPackLeadMax);
+    if (po->align != 1 && po->align != 16 && po->align != 64)
+        return fail(BT_E_INVALID_ARGUMENT, "align %u (1, 16 or 64)", po->align);
+    if (b->desc_format > BT_DESC_XDP) return fail(BT_E_INVALID_ARGUMENT, "unknown desc_format %u", b->desc_format);
+    if (b->n && !b->base) return fail(BT_E_INVALID_ARGUMENT, "null packet buffer");
+    if (!b->desc && b->stride == 0 && b->n) return fail(BT_E_INVALID_ARGUMENT, "fixed-stride mode needs stride > 0");
+    uint64_t bytes = b->bytes;
+    if (b->desc) {
+        if (!bytes) return fail(BT_E_INVALID_ARGUMENT, "descriptor batch with bytes == 0 (the readable size of base)");
+    } else {
+        const uint64_t need = (uint64_t)b->n * b->stride;
+        if (!bytes) bytes = need;
+        else if (bytes < need) return fail(BT_E_INVALID_ARGUMENT, "fixed-stride batch: bytes %llu < n * stride %llu",
+                                           (unsigned long long)bytes, (unsigned long long)need);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (b->n == 0) {
+        HIP_TRY(hipMemsetAsync(out->total, 0, 8, st));
+        HIP_TRY(hipMemsetAsync(out->n_packed, 0, 4, st));
+        return BT_OK;
+    }
+    int rc = ensure_ws(c, b->n);
+    if (rc) return rc;
+    bt_ctx::Ws* w = &c->ws[c->ws_next];
+    c->ws_next ^= 1;
+    if ((rc = ws_touch(c, w, st))) return rc;
+    PackArgs a{};
+    a.base = b->base;
+    a.desc = static_cast<const uint64_t*>(b->desc);
+    a.desc_words = b->desc_format == BT_DESC_XDP ? 2u : 1u;
+    a.stride = b->stride;
+    a.bytes = bytes;
+    a.n = b->n;
+    a.ntiles = (uint32_t)(((uint64_t)b->n + 63) / 64);
+    a.nchunks = (a.ntiles + kPackChunkTiles - 1) / kPackChunkTiles;
+    a.lead = po->lead;
+    a.snap = po->snap;
+    a.align = po->align;
+    a.select = select;
+    a.out = out->bytes;
+    a.cap = out->cap;
+    a.out_desc = out->desc;
+    a.total = out->total;
+    a.n_packed = out->n_packed;
+    a.sums = w->pack_sums;
+    rc = launch_pass_pack(a, st, e0, e1);
+    if (rc) return fail(rc, "pack kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return ws_done(c, w, st);
+}
+
+int bt_pass_pack_device(bt_ctx* c, const bt_batch* b, const uint64_t* select, const bt_pack_opts* po,
+                        const bt_pack_out* out, void* stream) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    return run_pass_pack(c, b, select, po, out, st, nullptr, nullptr);
+}
+
 int bt_parse_filter_device_async(bt_ctx* c, const bt_batch* b, const bt_outputs* o, void* stream,
                                  void* done_event) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
@@ -1135,6 +1215,39 @@ static int ensure_timing_events(bt_ctx* c, uint32_t iters) {
         HIP_TRY(hipEventCreate(&e));
         c->tev.push_back(e);
     }
+    return BT_OK;
+}
+
+int bt_time_pass_pack(bt_ctx* c, const bt_batch* b, const uint64_t* select, const bt_pack_opts* po,
+                      const bt_pack_out* out, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !b || !b->n || !iters || !ms) return fail(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int rc = run_pass_pack(c, b, select, po, out, c->stream, c->tev[2 * i], c->tev[2 * i + 1])) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->tev[2 * i], c->tev[2 * i + 1]));
+    return BT_OK;
+}
+
+int bt_time_copy_d2d(bt_ctx* c, void* dst, const void* src, uint64_t bytes, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !dst || !src || !bytes || !iters || !ms) return fail(BT_E_INVALID_ARGUMENT, "null argument / zero size");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i) {
+        HIP_TRY(hipEventRecord(c->tev[2 * i], c->stream));
+        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipEventRecord(c->tev[2 * i + 1], c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->tev[2 * i], c->tev[2 * i + 1]));
     return BT_OK;
 }
 

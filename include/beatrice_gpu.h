@@ -80,7 +80,8 @@ extern "C" {
  * bt_group_parse_filter_mapped / bt_group_split_cost / bt_context_placement added. Hosts
  * built against an older header should check bt_abi_version() >= the version they need.
  * Added within 2 (new entry points only, nothing existing changed; a host that needs them can
- * look the symbols up): bt_filter_resume_device, bt_ring_stage_tpv3_ex. */
+ * look the symbols up): bt_filter_resume_device, bt_ring_stage_tpv3_ex, bt_pass_pack_device,
+ * bt_pcap_index, bt_pcap_filter. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -415,6 +416,96 @@ int  bt_parse_filter_device(bt_ctx* ctx, const bt_batch* batch, const bt_outputs
  * argument, BT_BATCH_PREFIXES / BT_BATCH_LEAN set, records != NULL, decide == NULL, a
  * descriptor batch with bytes == 0. */
 int  bt_filter_resume_device(bt_ctx* ctx, const bt_batch* frames, const bt_outputs* out, void* stream);
+
+/* ---- the packets that passed: ordered pack of the selected frames ------------------
+ * Every path above ends in a verdict; this one produces the frames. The selected packets'
+ * bytes are packed in packet order into one buffer, on the GPU, so that only the survivors
+ * cross PCIe (or go on to the next stage). `select` has the verdict-word layout (bit i % 64
+ * of word i / 64; out->verdict of a filter call is one), device-visible like the rest; bits
+ * at or above n in the last word are ignored.
+ *   record k  = the k-th set bit's packet: `lead` bytes in front of the frame, then
+ *               min(len, snap ? snap : len) frame bytes;
+ *   its slot  = that size rounded up to `align`; the bytes between a record's end and its
+ *               slot's end are written as zeros;
+ *   its place = the sum of the earlier slots (64-bit).
+ * Source bytes outside [0, frames->bytes) read as zeros (a lead in front of the buffer, a
+ * descriptor running past it): the rule of bt_parse_filter_device; the kernel never reads
+ * outside the buffer. A slot is written only when it ends at or below `cap`: nothing is ever
+ * written at or past cap, *n_packed = the records of the longest prefix of the selection
+ * whose slots all fit (whole records only), and *total = the bytes the whole selection needs,
+ * whether it fits or not (total <= cap: everything was packed). Descriptor batches in both
+ * formats and fixed-stride batches (frame length min(stride, 65535)) are taken.
+ * BT_E_INVALID_ARGUMENT: a null argument (out->desc may be NULL; out->bytes may be NULL when
+ * cap is 0, a size query), lead > 64, align not 1, 16 or 64, BT_BATCH_PREFIXES / BT_BATCH_LEAN
+ * set (those batches hold no whole frames), a descriptor batch with bytes == 0.
+ * Asynchronous on `stream` (NULL = the context's stream); two kernel launches, no allocation
+ * once bt_reserve(n) has been called. */
+typedef struct bt_pack_opts {
+    uint32_t lead;     /* bytes in front of each frame copied with it (0..64): 16 over a pcap
+                          file takes each record header along                               */
+    uint32_t snap;     /* 0 = whole frames, else at most snap bytes of each frame            */
+    uint32_t align;    /* 1, 16 or 64: every output record (lead + frame) starts on a multiple;
+                          gap bytes are written as zeros                                     */
+    uint32_t reserved;
+} bt_pack_opts;
+typedef struct bt_pack_out {           /* device-visible memory                              */
+    uint8_t*     bytes;  uint64_t cap; /* packed output and its capacity                      */
+    bt_pkt_desc* desc;                 /* optional, n entries: entry k = BT_DESC(offset of record
+                                          k's frame (after its lead) in `bytes`, copied length),
+                                          for every selected packet, in order: with n_packed a
+                                          descriptor batch over `bytes`                       */
+    uint64_t*    total;                /* bytes the whole selection needs (even when > cap)   */
+    uint32_t*    n_packed;             /* records written: the longest prefix of the selection
+                                          that fits in cap, whole records only                */
+} bt_pack_out;
+int  bt_pass_pack_device(bt_ctx* ctx, const bt_batch* frames, const uint64_t* select,
+                         const bt_pack_opts* opts, const bt_pack_out* out, void* stream);
+
+/* ---- pcap capture files ------------------------------------------------------------
+ * Classic pcap (24-B global header, 16-B record headers), link type 1 (Ethernet), in all four
+ * magics: microsecond (0xa1b2c3d4) or nanosecond (0xa1b23c4d) timestamps, in the reader's
+ * byte order or swapped. bt_pcap_index is host only (no context, no device):
+ *   desc[i] = BT_DESC(offset of record i's data in the file, incl_len) for the first
+ *   min(*n, cap) records (desc == NULL: count only), *n = the whole records of the file.
+ * A file that ends inside a record header or inside a record's data is not an error: it is
+ * indexed up to its last whole record and info->truncated = 1.
+ * BT_E_NOT_IMPLEMENTED: another link type, a pcapng file. BT_E_INVALID_ARGUMENT: a null
+ * argument, fewer than 24 bytes, an unknown magic, a record with incl_len > 65535 (a
+ * descriptor holds 16 bits of length). */
+typedef struct bt_pcap_info {
+    uint32_t magic;        /* 0xa1b2c3d4 or 0xa1b23c4d (as the writer wrote it)                 */
+    uint32_t swapped;      /* 1: the header fields are in the other byte order                  */
+    uint32_t nanosecond;   /* 1: ts_usec holds nanoseconds                                      */
+    uint32_t snaplen;
+    uint32_t linktype;
+    uint32_t truncated;    /* 1: bytes after the last whole record that are no whole record     */
+    uint64_t end;          /* file offset just past the last whole record (24 with no records)  */
+} bt_pcap_info;
+int  bt_pcap_index(const uint8_t* file, uint64_t bytes, bt_pcap_info* info, bt_pkt_desc* desc,
+                   uint64_t cap, uint64_t* n);
+/* The capture filtered by the context's compiled program: `out` receives a pcap holding the
+ * input's 24-B global header, then the 16-B record header and the data of every packet whose
+ * decision is BT_DECIDE_PASS, verbatim and in order: byte for byte what a host loop over
+ * PacketFilter::applyFilters writing the passing records produces. The file is taken in
+ * chunks of whole records (at most the context's host_chunk_bytes and host_chunk_packets,
+ * and at most 64 MiB / 1M packets), double-buffered: pinned staging, H2D, the filter-only
+ * bt_parse_filter_device, bt_pass_pack_device with lead = 16 over its verdict words, and a
+ * D2H copy of exactly the packed bytes. A truncated file is filtered up to its last whole
+ * record (result->truncated = 1). out == NULL is the size query (result->out_bytes). An out_cap
+ * below the need returns BT_E_INVALID_ARGUMENT with result->out_bytes = the need (what fits in
+ * whole chunks has been written). A program with a BT_K_HOST slot (an installed CUSTOM
+ * callback, a PAYLOAD regex outside the GPU subset) is refused with BT_E_NOT_IMPLEMENTED
+ * before any work: the device alone cannot decide its packets. Synchronous; on an error the
+ * call's streams are idle when it returns and the first error is the one reported. */
+typedef struct bt_pcap_result {
+    uint64_t n_in;         /* whole records of the input                                        */
+    uint64_t n_pass, n_reject, n_throw;   /* by decision code; their sum is n_in                 */
+    uint64_t out_bytes;    /* bytes of the output pcap (24 + the passing records)               */
+    uint32_t truncated;
+    uint32_t chunks;       /* chunks the file was taken in                                      */
+} bt_pcap_result;
+int  bt_pcap_filter(bt_ctx* ctx, const uint8_t* file, uint64_t bytes, uint8_t* out, uint64_t out_cap,
+                    bt_pcap_result* result);
 
 /* Pipelined form for a stream of batches. The main kernel runs on `stream` as above
  * (records, decide and verdict are complete in stream order); the ordered compaction

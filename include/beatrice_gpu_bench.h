@@ -70,6 +70,15 @@ int  bt_time_device_ex(bt_ctx* ctx, const bt_batch* batch, const bt_outputs* out
 int  bt_time_device2(bt_ctx* ctx, const bt_batch* batch, const bt_outputs* out, uint32_t n_out,
                      uint32_t iters, uint32_t mode, bt_timing* timing);
 
+/* ---- timing of the ordered pack ------------------------------------------------- */
+/* bt_pass_pack_device `iters` times on the context's stream; ms[i] = launch i's two kernels,
+ * from an event pair recorded by their own dispatches. The outputs are those of the last launch. */
+int  bt_time_pass_pack(bt_ctx* ctx, const bt_batch* frames, const uint64_t* select, const bt_pack_opts* opts,
+                       const bt_pack_out* out, uint32_t iters, float* ms);
+/* A device-to-device hipMemcpyAsync of `bytes` on the context's stream, `iters` times, each
+ * between an event pair: the ceiling for moving that many bytes on the device. */
+int  bt_time_copy_d2d(bt_ctx* ctx, void* dst, const void* src, uint64_t bytes, uint32_t iters, float* ms);
+
 /* ---- timing of the user-protocol extractor ------------------------------------- */
 /* bt_extract_device `iters` times on the context's stream, each launch timed by an event
  * pair from its own dispatch packet (bt_timing.main_* = the extraction kernel). For
