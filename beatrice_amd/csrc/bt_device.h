@@ -5,6 +5,7 @@
 
 #include "beatrice_gpu.h"
 #include "bt_bounds.h"
+#include "bt_frames.h"
 
 namespace bt {
 
@@ -34,14 +35,7 @@ struct DevProgram {
 };
 
 // Everything the main kernel needs (passed by value as a kernel argument).
-struct MainArgs {
-    const uint8_t* base;
-    const uint64_t* desc;      // nullptr: fixed stride
-    uint32_t desc_words;       // descriptor stride in u64 words: 1 packed, 2 xdp_desc
-    uint64_t bytes;            // read limit from base: round_up(base + bytes, 16) - base (read_limit)
-    uint32_t stride;
-    uint32_t n;
-    uint32_t ntiles;           // ceil(n / 64): one wavefront tile = 64 packets
+struct MainArgs : FrameSrc {   // bytes = read_limit
     uint32_t n_cap;            // record plane stride (records)
     uint8_t* records;          // plane-major (or AoS when the AOS variant is launched)
     uint8_t* decide;
@@ -90,16 +84,9 @@ int launch_compact(const uint64_t* verdict, uint32_t n, uint32_t* chunk_sums, ui
 int device_grid_blocks(int device);
 
 // ---- second pass of the PAYLOAD filter over a prefix batch (bt_payload_resume.hip) ----
-// One batch of n WHOLE frames (base / desc / stride / bytes as in MainArgs) and the first pass's
-// decision bytes, rewritten in place where the code is BT_DECIDE_HOST at a BT_K_PAYLOAD slot.
-struct ResumeArgs {
-    const uint8_t* base;
-    const uint64_t* desc;      // nullptr: fixed stride
-    uint32_t desc_words;       // 1 packed, 2 xdp_desc
-    uint64_t bytes;            // read limit from base (read_limit)
-    uint32_t stride;
-    uint32_t n;
-    uint32_t ntiles;           // ceil(n / 64): the scan's unit
+// One batch of n WHOLE frames and the first pass's decision bytes, rewritten in place where the
+// code is BT_DECIDE_HOST at a BT_K_PAYLOAD slot.
+struct ResumeArgs : FrameSrc {   // bytes = read_limit; a tile is the scan's unit
     uint8_t* decide;           // n bytes, read and written
     const uint8_t* dfa;        // PAYLOAD DFA pool (device), copied to dynamic LDS per block
     uint32_t dfa_bytes;        // 0: no BT_K_PAYLOAD slot, nothing to do
@@ -158,12 +145,7 @@ struct ExTable {                      // kernel argument
     uint32_t row_dw;                  // LDS dwords per staged packet (set by launch_extract)
     ExField f[BT_FIELD_MAX];
 };
-struct ExArgs {
-    const uint8_t* base;
-    const uint64_t* desc;             // nullptr: fixed stride
-    uint32_t desc_words;
-    uint64_t bytes;                   // read limit from base (read_limit)
-    uint32_t stride, n, ntiles;
+struct ExArgs : FrameSrc {             // bytes = read_limit
     uint8_t* status;
     uint64_t* values;
     uint8_t* image;

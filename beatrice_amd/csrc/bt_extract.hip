@@ -137,20 +137,7 @@ __global__ __launch_bounds__(kBlock) void bt_extract_tile(ExArgs a, ExTable tab)
         const bool live = my < a.n;
         uint64_t off = 0;
         uint32_t len = 0;
-        if (live) {
-            if (!a.desc) {
-                off = (uint64_t)my * a.stride;
-                len = a.stride;
-            } else if (a.desc_words == 1) {
-                const uint64_t d = a.desc[my];
-                off = d & 0xFFFFFFFFFFFFull;
-                len = (uint32_t)(d >> 48);
-            } else {
-                const uint4 d = *reinterpret_cast<const uint4*>(a.desc + 2ull * my);
-                off = ((uint64_t)d.y << 32) | d.x;
-                len = d.z > 0xFFFFu ? 0xFFFFu : d.z;
-            }
-        }
+        if (live) frame_at(a, my, off, len);
         const bool ok = live && len >= span;
         const uint32_t s = (uint32_t)off & 15u;
         // ---- LOAD: [a0, off + min(len, window)) of every packet, 4 lanes per packet ----

@@ -578,15 +578,11 @@ int bt_group_parse_filter_mapped(bt_group* g, const bt_batch* b, const bt_output
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
     if (!g || !b || !o) return bt::set_error(BT_E_INVALID_ARGUMENT, "null argument");
     const uint32_t n = b->n;
-    if (n && !b->base) return bt::set_error(BT_E_INVALID_ARGUMENT, "null packet buffer");
-    if (!b->desc && b->stride == 0 && n) return bt::set_error(BT_E_INVALID_ARGUMENT, "fixed-stride mode needs stride > 0");
-    if (b->desc_format > BT_DESC_XDP) return bt::set_error(BT_E_INVALID_ARGUMENT, "unknown desc_format %u", b->desc_format);
-    if (b->desc && !b->bytes) return bt::set_error(BT_E_INVALID_ARGUMENT, "descriptor batch with bytes == 0");
     // fixed stride: the members' ranges are carved out of [base, base + n * stride), so a
-    // smaller stated size is refused here, as a single context refuses it (run_device)
-    if (!b->desc && b->bytes && b->bytes < (uint64_t)n * b->stride)
-        return bt::set_error(BT_E_INVALID_ARGUMENT, "fixed-stride batch: bytes %llu < n * stride %llu",
-                             (unsigned long long)b->bytes, (unsigned long long)n * b->stride);
+    // smaller stated size is refused here, as a single context refuses it
+    bt::FrameSrc fs{};
+    char why[128];
+    if (bt::frame_src(b, &fs, why, sizeof(why))) return bt::set_error(BT_E_INVALID_ARGUMENT, "%s", why);
     if (o->records && o->n_cap < n) return bt::set_error(BT_E_INVALID_ARGUMENT, "records n_cap %u < n %u", o->n_cap, n);
     const bool filter = o->verdict || o->decide || o->pass_idx || o->n_pass;
     const bool want_pass = o->pass_idx || o->n_pass;
@@ -602,7 +598,7 @@ int bt_group_parse_filter_mapped(bt_group* g, const bt_batch* b, const bt_output
         const bool aos = (flags & BT_OPT_RECORDS_AOS) != 0;
         if (o->records && (flags & BT_OPT_RECORDS_PLANES) && m > 1)
             return bt::set_error(BT_E_INVALID_ARGUMENT, "plane-major records cannot be split across group members");
-        const uint32_t dsz = !b->desc ? 0u : b->desc_format == BT_DESC_XDP ? 16u : 8u;
+        const uint32_t dsz = b->desc ? 8u * fs.desc_words : 0u;
         // the split: by what each packet costs its member's PCIe link
         std::vector<Range> r;
         if (m == 1) {
@@ -627,7 +623,7 @@ int bt_group_parse_filter_mapped(bt_group* g, const bt_batch* b, const bt_output
                              n, m, cost);
         }
         // the verdict words the pass list is built from
-        const uint32_t words = (n + 63) / 64;
+        const uint32_t words = fs.ntiles;
         std::unique_lock<std::mutex> slk(g->scratch_mu, std::defer_lock);
         uint64_t* ver = o->verdict;
         std::vector<uint8_t*> ver_dev(m, nullptr);
@@ -678,7 +674,7 @@ int bt_group_parse_filter_mapped(bt_group* g, const bt_batch* b, const bt_output
         for (uint32_t k = 0; k < m; ++k) {
             const uint32_t lo = r[k].lo, cnt = r[k].hi - r[k].lo;
             uint8_t *base = nullptr, *desc = nullptr, *rec = nullptr, *dec = nullptr, *vw = nullptr;
-            if (int rc = need(b->base, b->bytes ? b->bytes : (uint64_t)n * b->stride, "batch.base", k, &base)) return rc;
+            if (int rc = need(b->base, fs.bytes, "batch.base", k, &base)) return rc;
             if (int rc = need(b->desc, (uint64_t)n * dsz, "batch.desc", k, &desc)) return rc;
             if (int rc = need(o->records, rec_bytes, "out.records", k, &rec)) return rc;
             if (int rc = need(o->decide, n, "out.decide", k, &dec)) return rc;
@@ -695,7 +691,7 @@ int bt_group_parse_filter_mapped(bt_group* g, const bt_batch* b, const bt_output
                 x.b.desc = desc + (size_t)lo * dsz;
             } else {
                 x.b.base = base + (size_t)lo * b->stride;
-                x.b.bytes = (b->bytes ? b->bytes : (uint64_t)n * b->stride) - (uint64_t)lo * b->stride;
+                x.b.bytes = fs.bytes - (uint64_t)lo * b->stride;
             }
             if (rec) {
                 x.o.records = aos ? rec + (size_t)lo * BT_REC_BYTES : rec + (size_t)(lo / kTile) * 6144;

@@ -485,13 +485,10 @@ __device__ __forceinline__ void issue_loads(const MainArgs& a, uint32_t t, uint3
     } else {
         if (a.desc) {
             if (a.desc_words == 1) {   // bt_pkt_desc
-                const uint64_t d = live ? a.desc[my] : 0ull;
-                st.off = d & 0xFFFFFFFFFFFFull;
-                st.len = (uint32_t)(d >> 48);
+                desc_packed(live ? a.desc[my] : 0ull, st.off, st.len);
             } else {                   // xdp_desc {u64 addr; u32 len; u32 options}
                 const uint4 d = live ? *reinterpret_cast<const uint4*>(a.desc + 2ull * my) : make_uint4(0, 0, 0, 0);
-                st.off = ((uint64_t)d.y << 32) | d.x;
-                st.len = d.z > 0xFFFFu ? 0xFFFFu : d.z;
+                desc_xdp(((uint64_t)d.y << 32) | d.x, d.z, st.off, st.len);
             }
         } else {
             st.off = live ? (uint64_t)my * a.stride : 0ull;
@@ -929,13 +926,9 @@ __device__ __forceinline__ void load_desc_pipe(const MainArgs& a, uint32_t t, bo
 
 template <int DW>
 __device__ __forceinline__ void decode_desc(const uint32_t (&w)[DW + 1], uint64_t& off, uint32_t& len) {
-    if constexpr (DW == 1) {   // bt_pkt_desc: off in bits 0..47, len in 48..63
-        off = ((uint64_t)(w[1] & 0xFFFFu) << 32) | w[0];
-        len = w[1] >> 16;
-    } else {                   // xdp_desc {u64 addr; u32 len; u32 options}
-        off = ((uint64_t)w[1] << 32) | w[0];
-        len = w[2] > 0xFFFFu ? 0xFFFFu : w[2];
-    }
+    const uint64_t d = ((uint64_t)w[1] << 32) | w[0];
+    if constexpr (DW == 1) desc_packed(d, off, len);
+    else desc_xdp(d, w[2], off, len);
 }
 
 // Round A of tile t from descriptors already in registers (issue_loads' loads, with the

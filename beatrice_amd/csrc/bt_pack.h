@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "beatrice_gpu.h"
+#include "bt_frames.h"
 
 namespace bt {
 
@@ -19,14 +20,7 @@ struct PackChunkSum {          // workspace, one per chunk: written by bt_pack_s
     uint64_t count;            // the chunk's selected packets
 };
 
-struct PackArgs {
-    const uint8_t* base;
-    const uint64_t* desc;      // nullptr: fixed stride
-    uint32_t desc_words;       // 1 packed, 2 xdp_desc
-    uint32_t stride;
-    uint64_t bytes;            // the readable size of base: source bytes outside [0, bytes) are zeros
-    uint32_t n;
-    uint32_t ntiles;           // ceil(n / 64)
+struct PackArgs : FrameSrc {   // bytes = the exact readable size: source bytes outside [0, bytes) are zeros
     uint32_t nchunks;          // ceil(ntiles / kPackChunkTiles)
     uint32_t lead, snap, align;
     const uint64_t* select;    // ntiles words; bits at or above n are ignored

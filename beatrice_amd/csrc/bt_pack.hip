@@ -56,20 +56,8 @@ __device__ __forceinline__ uint64_t select_word(const PackArgs& a, uint32_t t) {
 
 // Packet i: the source offset of its frame and the frame bytes copied.
 __device__ __forceinline__ void frame_of(const PackArgs& a, uint32_t i, uint64_t& off, uint32_t& len) {
-    if (a.desc) {
-        if (a.desc_words == 1) {   // bt_pkt_desc
-            const uint64_t d = a.desc[i];
-            off = d & 0xFFFFFFFFFFFFull;
-            len = (uint32_t)(d >> 48);
-        } else {                   // xdp_desc {u64 addr; u32 len; u32 options}
-            const uint4 d = *reinterpret_cast<const uint4*>(a.desc + 2ull * i);
-            off = ((uint64_t)d.y << 32) | d.x;
-            len = d.z > 0xFFFFu ? 0xFFFFu : d.z;
-        }
-    } else {
-        off = (uint64_t)i * a.stride;
-        len = a.stride > 0xFFFFu ? 0xFFFFu : a.stride;
-    }
+    frame_at(a, i, off, len);
+    if (len > 0xFFFFu) len = 0xFFFFu;   // a fixed stride: record lengths are 16-bit
     if (a.snap && len > a.snap) len = a.snap;
 }
 

@@ -71,20 +71,7 @@ __device__ __forceinline__ void resume_items(const ResumeArgs& a, const DevProgr
     uint32_t len = 0, slot0 = 0;
     if (have && BT_IN(&g_bounds_resume, kSiteDecide, idx, a.n)) {
         slot0 = BT_DECIDE_SLOT(a.decide[idx]);
-        if (a.desc) {
-            if (a.desc_words == 1) {   // bt_pkt_desc
-                const uint64_t d = a.desc[idx];
-                off = d & 0xFFFFFFFFFFFFull;
-                len = (uint32_t)(d >> 48);
-            } else {                   // xdp_desc {u64 addr; u32 len; u32 options}
-                const uint4 d = *reinterpret_cast<const uint4*>(a.desc + 2ull * idx);
-                off = ((uint64_t)d.y << 32) | d.x;
-                len = d.z > 0xFFFFu ? 0xFFFFu : d.z;
-            }
-        } else {
-            off = (uint64_t)idx * a.stride;
-            len = a.stride;
-        }
+        frame_at(a, idx, off, len);
     }
     const uint32_t s = (uint32_t)off & 15u;
     const uint32_t off_lo = (uint32_t)off, off_hi = (uint32_t)(off >> 32);

@@ -7,25 +7,23 @@
 #include <stdint.h>
 
 #include "beatrice_gpu.h"
+#include "bt_frames.h"
 
 namespace bt {
 
-// What bt_filter_resume_device refuses, as the message of its BT_E_INVALID_ARGUMENT; nullptr when
-// the arguments are acceptable.
-inline const char* resume_args_error(const bt_ctx* ctx, const bt_batch* frames, const bt_outputs* out) {
+// What bt_filter_resume_device refuses, as the message of its BT_E_INVALID_ARGUMENT (valid until
+// the thread's next call); nullptr when the arguments are acceptable, with *fs = the frames.
+inline const char* resume_args_error(const bt_ctx* ctx, const bt_batch* frames, const bt_outputs* out,
+                                     FrameSrc* fs = nullptr) {
     if (!ctx || !frames || !out) return "bt_filter_resume_device: null argument";
     if (frames->flags & (BT_BATCH_PREFIXES | BT_BATCH_LEAN))
         return "bt_filter_resume_device: the resume pass reads whole frames (BT_BATCH_PREFIXES set)";
     if (out->records) return "bt_filter_resume_device: records must be NULL (the first pass wrote what it could)";
     if (!out->decide) return "bt_filter_resume_device: decide == NULL (the first pass's decision bytes)";
-    if (frames->desc_format > BT_DESC_XDP) return "bt_filter_resume_device: unknown desc_format";
-    if (frames->n && !frames->base) return "bt_filter_resume_device: null packet buffer";
-    if (frames->desc && !frames->bytes)
-        return "bt_filter_resume_device: descriptor batch with bytes == 0 (the readable size of base)";
-    if (!frames->desc && frames->n && !frames->stride) return "bt_filter_resume_device: fixed-stride mode needs stride > 0";
-    if (!frames->desc && frames->bytes && frames->bytes < (uint64_t)frames->n * frames->stride)
-        return "bt_filter_resume_device: fixed-stride batch: bytes < n * stride";
-    return nullptr;
+    thread_local char msg[160];
+    const int k = snprintf(msg, sizeof(msg), "bt_filter_resume_device: ");
+    FrameSrc mine;
+    return frame_src(frames, fs ? fs : &mine, msg + k, sizeof(msg) - (size_t)k) ? msg : nullptr;
 }
 
 // Verdict words [w_lo, w_hi) of n decision bytes: bit i of word j = frame 64 j + i has code

@@ -38,20 +38,10 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 #define HIP_TRY(x)                                                                       \
     do {                                                                                 \
         hipError_t e_ = (x);                                                             \
-        if (e_ != hipSuccess) return fail(BT_E_INTERNAL, "%s: %s", #x, hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) return set_error(BT_E_INTERNAL, "%s: %s", #x, hipGetErrorString(e_)); \
     } while (0)
 
 constexpr uint32_t kHostSlot = 112;   // bytes of each frame staged for the device (>= kNeedParse + pad)
@@ -372,6 +362,14 @@ int ensure_ws(bt_ctx* c, uint32_t n) {
     return BT_OK;
 }
 
+// The workspace buffer of a call over n packets (consecutive calls alternate).
+int take_ws(bt_ctx* c, uint32_t n, bt_ctx::Ws** w) {
+    if (int rc = ensure_ws(c, n)) return rc;
+    *w = &c->ws[c->ws_next];
+    c->ws_next ^= 1;
+    return BT_OK;
+}
+
 bool ctx_stream(const bt_ctx* c, hipStream_t s) { return s == c->stream || (c->cstream && s == c->cstream); }
 
 // `s` is about to queue work that touches workspace buffer w: if another stream did last,
@@ -430,8 +428,8 @@ int check_bounds(hipStream_t st, hipStream_t cst, const char* what) {
         fprintf(stderr, "BT_DEBUG_BOUNDS: %s: %u failed checks, first %s (site %u) block %u thread %u index %llu "
                 "limit %llu\n", what, k, bounds_site_name(f.site), f.site, f.block, f.lane,
                 (unsigned long long)f.index, (unsigned long long)f.limit);
-        return fail(BT_E_INTERNAL, "BT_DEBUG_BOUNDS: %s: %u failed checks, first %s index %llu limit %llu", what, k,
-                    bounds_site_name(f.site), (unsigned long long)f.index, (unsigned long long)f.limit);
+        return set_error(BT_E_INTERNAL, "BT_DEBUG_BOUNDS: %s: %u failed checks, first %s index %llu limit %llu", what, k,
+                         bounds_site_name(f.site), (unsigned long long)f.index, (unsigned long long)f.limit);
     }
 #else
     (void)st;
@@ -464,13 +462,15 @@ int dfa_read_on(bt_ctx* c, hipStream_t st) {
 // recorded after the compaction on cst.
 int run_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, hipStream_t st, bool aos,
                hipEvent_t e0, hipEvent_t e1, hipStream_t cst = nullptr, hipEvent_t done = nullptr) {
-    if (!b || !o) return fail(BT_E_INVALID_ARGUMENT, "null batch/outputs");
-    if (b->n && !b->base) return fail(BT_E_INVALID_ARGUMENT, "null packet buffer");
-    if (!b->desc && b->stride == 0 && b->n) return fail(BT_E_INVALID_ARGUMENT, "fixed-stride mode needs stride > 0");
+    if (!b || !o) return set_error(BT_E_INVALID_ARGUMENT, "null batch/outputs");
+    MainArgs a{};
+    char why[128];
+    const FrameCheck bad = frame_src(b, &a, why, sizeof(why));
+    if (bad == kFramesUnusable) return set_error(BT_E_INVALID_ARGUMENT, "%s", why);
     // the calling thread's current device may be another context's (a group's member threads,
     // a host driving several devices): launches, events and allocations below are this one's
     HIP_TRY(hipSetDevice(c->device));
-    if (o->records && o->n_cap < b->n) return fail(BT_E_INVALID_ARGUMENT, "records n_cap %u < n %u", o->n_cap, b->n);
+    if (o->records && o->n_cap < b->n) return set_error(BT_E_INVALID_ARGUMENT, "records n_cap %u < n %u", o->n_cap, b->n);
     const bool filter = o->verdict || o->decide || o->pass_idx || o->n_pass;
     const bool compact = o->pass_idx || o->n_pass;
     if (!filter && !o->records) return BT_OK;
@@ -481,36 +481,12 @@ int run_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, hipStream_t st
         return BT_OK;
     }
     bt_ctx::Ws* w = nullptr;
-    if (compact) {
-        int rc = ensure_ws(c, b->n);
-        if (rc) return rc;
-        w = &c->ws[c->ws_next];
-        c->ws_next ^= 1;
-    }
-    if (b->desc_format > BT_DESC_XDP) return fail(BT_E_INVALID_ARGUMENT, "unknown desc_format %u", b->desc_format);
+    if (int rc = compact ? take_ws(c, b->n, &w) : BT_OK) return rc;
+    if (bad) return set_error(BT_E_INVALID_ARGUMENT, "%s", why);
     if ((b->flags & BT_BATCH_LEAN) && o->records)
-        return fail(BT_E_INVALID_ARGUMENT, "a BT_BATCH_LEAN batch holds frame bytes 12..43 only: no records");
-    // The readable range of base is part of the contract: descriptor batches must state it
-    // (a descriptor past it then reads zeros instead of arbitrary memory); fixed-stride
-    // batches default to n * stride.
-    uint64_t bytes = b->bytes;
-    if (b->desc) {
-        if (!bytes) return fail(BT_E_INVALID_ARGUMENT, "descriptor batch with bytes == 0 (the readable size of base)");
-    } else {
-        const uint64_t need = (uint64_t)b->n * b->stride;
-        if (!bytes) bytes = need;
-        else if (bytes < need) return fail(BT_E_INVALID_ARGUMENT, "fixed-stride batch: bytes %llu < n * stride %llu",
-                                           (unsigned long long)bytes, (unsigned long long)need);
-    }
-    MainArgs a{};
-    a.base = b->base;
-    a.desc = static_cast<const uint64_t*>(b->desc);
-    a.desc_words = b->desc_format == BT_DESC_XDP ? 2u : 1u;
+        return set_error(BT_E_INVALID_ARGUMENT, "a BT_BATCH_LEAN batch holds frame bytes 12..43 only: no records");
+    a.bytes = read_limit(a.base, a.bytes);
     a.prefixes = (b->flags & (BT_BATCH_PREFIXES | BT_BATCH_LEAN)) ? 1u : 0u;
-    a.stride = b->stride;
-    a.n = b->n;
-    a.ntiles = (b->n + 63) / 64;
-    a.bytes = read_limit(b->base, bytes);
     a.n_cap = o->records ? o->n_cap : 0;
     a.records = reinterpret_cast<uint8_t*>(o->records);
     a.decide = o->decide;
@@ -575,14 +551,14 @@ int run_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, hipStream_t st
         c->md_next = (c->md_next + 1) % bt_ctx::kMainDone;
     }
     int rc = launch_main(a, c->prog, rec, filter, c->grid, !(c->opts.flags & BT_OPT_NO_PREFETCH), st, e0, mend);
-    if (rc) return fail(rc, "main kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return set_error(rc, "main kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     if (w && !o->verdict) { if ((rc = ws_done(c, w, st))) return rc; }
     if (a.dfa_bytes && (rc = dfa_read_on(c, st))) return rc;
     if (compact) {
         if (piped) HIP_TRY(hipStreamWaitEvent(cst, mend, 0));
         if ((rc = ws_touch(c, w, cst))) return rc;
         rc = launch_compact(a.verdict, b->n, w->chunk_sums, o->pass_idx, o->n_pass, cst);
-        if (rc) return fail(rc, "compaction launch failed");
+        if (rc) return set_error(rc, "compaction launch failed");
         if ((rc = ws_done(c, w, cst))) return rc;
         if (done) HIP_TRY(hipEventRecord(done, cst));
     } else if (done) {
@@ -762,7 +738,7 @@ int bt_abi_version(void) { return BT_ABI_VERSION; }
 const char* bt_last_error(void) { return g_err.c_str(); }
 
 int bt_device_count(int* out) {
-    if (!out) return fail(BT_E_INVALID_ARGUMENT, "null out");
+    if (!out) return set_error(BT_E_INVALID_ARGUMENT, "null out");
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess) n = 0;
@@ -772,12 +748,12 @@ int bt_device_count(int* out) {
 
 int bt_create(int device, const bt_opts* opts, bt_ctx** out) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!out) return fail(BT_E_INVALID_ARGUMENT, "null out");
+    if (!out) return set_error(BT_E_INVALID_ARGUMENT, "null out");
     *out = nullptr;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        return fail(BT_E_INIT_FAILED, "no HIP device visible (the MI355X path needs a GPU)");
-    if (device < 0 || device >= n) return fail(BT_E_INVALID_ARGUMENT, "device %d out of range [0,%d)", device, n);
+        return set_error(BT_E_INIT_FAILED, "no HIP device visible (the MI355X path needs a GPU)");
+    if (device < 0 || device >= n) return set_error(BT_E_INVALID_ARGUMENT, "device %d out of range [0,%d)", device, n);
     auto* c = new bt_ctx();
     c->device = device;
     if (opts) c->opts = *opts;
@@ -790,7 +766,7 @@ int bt_create(int device, const bt_opts* opts, bt_ctx** out) {
     }
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
-        return fail(BT_E_INIT_FAILED, "hipSetDevice/hipStreamCreate failed on device %d", device);
+        return set_error(BT_E_INIT_FAILED, "hipSetDevice/hipStreamCreate failed on device %d", device);
     }
     (void)hipGetDeviceFlags(&c->device_flags);
     (void)hipEventCreate(&c->ev0);
@@ -805,17 +781,17 @@ int bt_create(int device, const bt_opts* opts, bt_ctx** out) {
 }
 
 int bt_context_device(const bt_ctx* c, int* device, char* pci_bus_id, uint32_t cap) {
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
     if (device) *device = c->device;
     if (pci_bus_id) {
-        if (cap < 16) return fail(BT_E_INVALID_ARGUMENT, "pci_bus_id buffer of %u bytes (need >= 16)", cap);
+        if (cap < 16) return set_error(BT_E_INVALID_ARGUMENT, "pci_bus_id buffer of %u bytes (need >= 16)", cap);
         HIP_TRY(hipDeviceGetPCIBusId(pci_bus_id, (int)cap, c->device));
     }
     return BT_OK;
 }
 
 int bt_context_placement(bt_ctx* c, bt_placement* out) {
-    if (!c || !out) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!c || !out) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     *out = bt_placement{};
     out->numa_node = c->numa_node;
     out->pinned_cpus = c->pinned ? (uint32_t)CPU_COUNT(&c->pin) : 0u;
@@ -831,7 +807,7 @@ int bt_context_placement(bt_ctx* c, bt_placement* out) {
 }
 
 int bt_node_cpus(int node, int32_t* cpus, uint32_t cap, uint32_t* n) {
-    if (!n || (cap && !cpus)) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!n || (cap && !cpus)) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     *n = 0;
     cpu_set_t s;
     if (!bt::node_cpus(node, &s)) return BT_OK;
@@ -890,10 +866,10 @@ void bt_destroy(bt_ctx* c) {
 
 int bt_filter_compile_host(const bt_filter_desc* f, uint32_t n, bt_filter_slot* out, uint32_t cap,
                            uint32_t* n_slots) {
-    if ((!f && n) || !out || !n_slots) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if ((!f && n) || !out || !n_slots) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     char err[256] = {0};
     int rc = compile_filters(f, n, out, cap, n_slots, err, sizeof(err));
-    if (rc) return fail(rc, "%s", err);
+    if (rc) return set_error(rc, "%s", err);
     return BT_OK;
 }
 
@@ -998,14 +974,14 @@ extern "C" {
 
 int bt_filter_compile(bt_ctx* c, const bt_filter_desc* f, uint32_t n) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
     CompiledProgram p;
     if (int rc = compile_program(f, n, c->opts.flags, &p)) return rc;
     return install_program(c, p);
 }
 
 int bt_filter_program(const bt_ctx* c, bt_filter_slot* out, uint32_t cap, uint32_t* n_slots) {
-    if (!c || !n_slots) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!c || !n_slots) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     *n_slots = (uint32_t)c->slots.size();
     for (uint32_t i = 0; i < c->slots.size() && i < cap && out; ++i) out[i] = c->slots[i];
     return BT_OK;
@@ -1013,14 +989,14 @@ int bt_filter_program(const bt_ctx* c, bt_filter_slot* out, uint32_t cap, uint32
 
 int bt_reserve(bt_ctx* c, uint32_t n) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
     std::lock_guard<std::mutex> lk(c->mu);
     return ensure_ws(c, n);
 }
 
 int bt_parse_filter_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, void* stream) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
     return run_device(c, b, o, st, false, nullptr, nullptr);
@@ -1030,7 +1006,8 @@ int bt_parse_filter_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, vo
 // program has a BT_K_PAYLOAD slot, then the verdict words and the pass list from the final bytes.
 int bt_filter_resume_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, void* stream) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (const char* why = resume_args_error(c, b, o)) return fail(BT_E_INVALID_ARGUMENT, "%s", why);
+    ResumeArgs a{};
+    if (const char* why = resume_args_error(c, b, o, &a)) return set_error(BT_E_INVALID_ARGUMENT, "%s", why);
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
     HIP_TRY(hipSetDevice(c->device));
@@ -1039,33 +1016,24 @@ int bt_filter_resume_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, v
         if (o->n_pass) HIP_TRY(hipMemsetAsync(o->n_pass, 0, 4, st));
         return BT_OK;
     }
-    ResumeArgs a{};
-    a.base = b->base;
-    a.desc = static_cast<const uint64_t*>(b->desc);
-    a.desc_words = b->desc_format == BT_DESC_XDP ? 2u : 1u;
-    a.bytes = read_limit(b->base, b->desc || b->bytes ? b->bytes : (uint64_t)b->n * b->stride);
-    a.stride = b->stride;
-    a.n = b->n;
-    a.ntiles = (b->n + 63) / 64;
+    a.bytes = read_limit(a.base, a.bytes);
     a.decide = o->decide;
     a.dfa = c->dfa_dev[c->dfa_cur];
     a.dfa_bytes = (uint32_t)c->dfa_pool.size();
     int rc = launch_payload_resume(a, c->prog, st);
-    if (rc) return fail(rc, "resume kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return set_error(rc, "resume kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     if (a.dfa_bytes && (rc = dfa_read_on(c, st))) return rc;
     if (o->verdict || compact) {
         bt_ctx::Ws* w = nullptr;
         if (compact) {
-            if ((rc = ensure_ws(c, b->n))) return rc;
-            w = &c->ws[c->ws_next];
-            c->ws_next ^= 1;
+            if ((rc = take_ws(c, b->n, &w))) return rc;
             if ((rc = ws_touch(c, w, st))) return rc;
         }
         uint64_t* words = o->verdict ? o->verdict : w->verdict;
-        if ((rc = launch_verdict_words(o->decide, b->n, words, st))) return fail(rc, "verdict kernel launch failed");
+        if ((rc = launch_verdict_words(o->decide, b->n, words, st))) return set_error(rc, "verdict kernel launch failed");
         if (compact) {
             rc = launch_compact(words, b->n, w->chunk_sums, o->pass_idx, o->n_pass, st);
-            if (rc) return fail(rc, "compaction launch failed");
+            if (rc) return set_error(rc, "compaction launch failed");
             if ((rc = ws_done(c, w, st))) return rc;
         }
     }
@@ -1077,44 +1045,26 @@ int bt_filter_resume_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, v
 static int run_pass_pack(bt_ctx* c, const bt_batch* b, const uint64_t* select, const bt_pack_opts* po,
                          const bt_pack_out* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
     if (!c || !b || !select || !po || !out || !out->total || !out->n_packed)
-        return fail(BT_E_INVALID_ARGUMENT, "null argument");
-    if (!out->bytes && out->cap) return fail(BT_E_INVALID_ARGUMENT, "null output with cap %llu", (unsigned long long)out->cap);
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!out->bytes && out->cap) return set_error(BT_E_INVALID_ARGUMENT, "null output with cap %llu", (unsigned long long)out->cap);
     if (b->flags & (BT_BATCH_PREFIXES | BT_BATCH_LEAN))
-        return fail(BT_E_INVALID_ARGUMENT, "a BT_BATCH_PREFIXES / BT_BATCH_LEAN batch holds no whole frames to pack");
-    if (po->lead > kPackLeadMax) return fail(BT_E_INVALID_ARGUMENT, "lead %u > %u", po->lead, kPackLeadMax);
+        return set_error(BT_E_INVALID_ARGUMENT, "a BT_BATCH_PREFIXES / BT_BATCH_LEAN batch holds no whole frames to pack");
+    if (po->lead > kPackLeadMax) return set_error(BT_E_INVALID_ARGUMENT, "lead %u > %u", po->lead, kPackLeadMax);
     if (po->align != 1 && po->align != 16 && po->align != 64)
-        return fail(BT_E_INVALID_ARGUMENT, "align %u (1, 16 or 64)", po->align);
-    if (b->desc_format > BT_DESC_XDP) return fail(BT_E_INVALID_ARGUMENT, "unknown desc_format %u", b->desc_format);
-    if (b->n && !b->base) return fail(BT_E_INVALID_ARGUMENT, "null packet buffer");
-    if (!b->desc && b->stride == 0 && b->n) return fail(BT_E_INVALID_ARGUMENT, "fixed-stride mode needs stride > 0");
-    uint64_t bytes = b->bytes;
-    if (b->desc) {
-        if (!bytes) return fail(BT_E_INVALID_ARGUMENT, "descriptor batch with bytes == 0 (the readable size of base)");
-    } else {
-        const uint64_t need = (uint64_t)b->n * b->stride;
-        if (!bytes) bytes = need;
-        else if (bytes < need) return fail(BT_E_INVALID_ARGUMENT, "fixed-stride batch: bytes %llu < n * stride %llu",
-                                           (unsigned long long)bytes, (unsigned long long)need);
-    }
+        return set_error(BT_E_INVALID_ARGUMENT, "align %u (1, 16 or 64)", po->align);
+    PackArgs a{};
+    char why[128];
+    if (frame_src(b, &a, why, sizeof(why))) return set_error(BT_E_INVALID_ARGUMENT, "%s", why);
     HIP_TRY(hipSetDevice(c->device));
     if (b->n == 0) {
         HIP_TRY(hipMemsetAsync(out->total, 0, 8, st));
         HIP_TRY(hipMemsetAsync(out->n_packed, 0, 4, st));
         return BT_OK;
     }
-    int rc = ensure_ws(c, b->n);
+    bt_ctx::Ws* w = nullptr;
+    int rc = take_ws(c, b->n, &w);
     if (rc) return rc;
-    bt_ctx::Ws* w = &c->ws[c->ws_next];
-    c->ws_next ^= 1;
     if ((rc = ws_touch(c, w, st))) return rc;
-    PackArgs a{};
-    a.base = b->base;
-    a.desc = static_cast<const uint64_t*>(b->desc);
-    a.desc_words = b->desc_format == BT_DESC_XDP ? 2u : 1u;
-    a.stride = b->stride;
-    a.bytes = bytes;
-    a.n = b->n;
-    a.ntiles = (uint32_t)(((uint64_t)b->n + 63) / 64);
     a.nchunks = (a.ntiles + kPackChunkTiles - 1) / kPackChunkTiles;
     a.lead = po->lead;
     a.snap = po->snap;
@@ -1127,14 +1077,14 @@ static int run_pass_pack(bt_ctx* c, const bt_batch* b, const uint64_t* select, c
     a.n_packed = out->n_packed;
     a.sums = w->pack_sums;
     rc = launch_pass_pack(a, st, e0, e1);
-    if (rc) return fail(rc, "pack kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return set_error(rc, "pack kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     return ws_done(c, w, st);
 }
 
 int bt_pass_pack_device(bt_ctx* c, const bt_batch* b, const uint64_t* select, const bt_pack_opts* po,
                         const bt_pack_out* out, void* stream) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
     return run_pass_pack(c, b, select, po, out, st, nullptr, nullptr);
@@ -1143,7 +1093,7 @@ int bt_pass_pack_device(bt_ctx* c, const bt_batch* b, const uint64_t* select, co
 int bt_parse_filter_device_async(bt_ctx* c, const bt_batch* b, const bt_outputs* o, void* stream,
                                  void* done_event) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
     std::lock_guard<std::mutex> lk(c->mu);
     if (int rc = ensure_cstream(c)) return rc;
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
@@ -1221,7 +1171,7 @@ static int ensure_timing_events(bt_ctx* c, uint32_t iters) {
 int bt_time_pass_pack(bt_ctx* c, const bt_batch* b, const uint64_t* select, const bt_pack_opts* po,
                       const bt_pack_out* out, uint32_t iters, float* ms) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c || !b || !b->n || !iters || !ms) return fail(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    if (!c || !b || !b->n || !iters || !ms) return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_timing_events(c, iters)) return rc;
@@ -1237,7 +1187,7 @@ int bt_time_pass_pack(bt_ctx* c, const bt_batch* b, const uint64_t* select, cons
 
 int bt_time_copy_d2d(bt_ctx* c, void* dst, const void* src, uint64_t bytes, uint32_t iters, float* ms) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c || !dst || !src || !bytes || !iters || !ms) return fail(BT_E_INVALID_ARGUMENT, "null argument / zero size");
+    if (!c || !dst || !src || !bytes || !iters || !ms) return set_error(BT_E_INVALID_ARGUMENT, "null argument / zero size");
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_timing_events(c, iters)) return rc;
@@ -1254,8 +1204,8 @@ int bt_time_copy_d2d(bt_ctx* c, void* dst, const void* src, uint64_t bytes, uint
 int bt_time_device2(bt_ctx* c, const bt_batch* b, const bt_outputs* outs, uint32_t n_out, uint32_t iters,
                     uint32_t mode, bt_timing* t) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c || !b || !outs || !n_out || !iters) return fail(BT_E_INVALID_ARGUMENT, "null argument / zero iterations");
-    if (mode & ~(uint32_t)(BT_TIME_KERNEL_EVENTS | BT_TIME_PIPELINED)) return fail(BT_E_INVALID_ARGUMENT, "unknown mode");
+    if (!c || !b || !outs || !n_out || !iters) return set_error(BT_E_INVALID_ARGUMENT, "null argument / zero iterations");
+    if (mode & ~(uint32_t)(BT_TIME_KERNEL_EVENTS | BT_TIME_PIPELINED)) return set_error(BT_E_INVALID_ARGUMENT, "unknown mode");
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     const bool kev = (mode & BT_TIME_KERNEL_EVENTS) != 0;
@@ -1278,10 +1228,10 @@ int bt_time_device2(bt_ctx* c, const bt_batch* b, const bt_outputs* outs, uint32
         for (uint32_t i = 0; rc == BT_OK && i < iters; ++i) rc = run_device(c, b, o, c->stream, false, nullptr, nullptr);
         hipError_t ee = hipStreamEndCapture(c->stream, &g);
         if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-        if (ee != hipSuccess || !g) return fail(BT_E_INTERNAL, "graph capture failed: %s", hipGetErrorString(ee));
+        if (ee != hipSuccess || !g) return set_error(BT_E_INTERNAL, "graph capture failed: %s", hipGetErrorString(ee));
         hipError_t e = hipGraphInstantiate(&c->tgraph, g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
-        if (e != hipSuccess) { c->tgraph = nullptr; return fail(BT_E_INTERNAL, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) { c->tgraph = nullptr; return set_error(BT_E_INTERNAL, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
         c->tg_batch = *b;
         c->tg_out = *o;
         c->tg_iters = iters;
@@ -1552,8 +1502,8 @@ extern "C" {
 int bt_parse_filter(bt_ctx* c, const uint8_t* base, const bt_pkt_desc* desc, uint32_t n, bt_rec* records,
                     uint64_t* verdict, uint8_t* decide, uint32_t* pass_idx, uint32_t* n_pass) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
-    if (n && (!base || !desc)) return fail(BT_E_INVALID_ARGUMENT, "null packet buffer/descriptors");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
+    if (n && (!base || !desc)) return set_error(BT_E_INVALID_ARGUMENT, "null packet buffer/descriptors");
     const WaitFor lk(c);
     return host_pipeline(
         c, n,
@@ -1567,10 +1517,10 @@ int bt_parse_filter(bt_ctx* c, const uint8_t* base, const bt_pkt_desc* desc, uin
 int bt_parse_filter_ptrs(bt_ctx* c, const uint8_t* const* frames, const uint32_t* lens, uint32_t n,
                          bt_rec* records, uint64_t* verdict, uint8_t* decide, uint32_t* pass_idx, uint32_t* n_pass) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
-    if (n && (!frames || !lens)) return fail(BT_E_INVALID_ARGUMENT, "null frame pointers/lengths");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
+    if (n && (!frames || !lens)) return set_error(BT_E_INVALID_ARGUMENT, "null frame pointers/lengths");
     for (uint32_t i = 0; i < n; ++i)
-        if (lens[i] > 0xFFFFu) return fail(BT_E_INVALID_ARGUMENT, "frame %u longer than 65535 bytes", i);
+        if (lens[i] > 0xFFFFu) return set_error(BT_E_INVALID_ARGUMENT, "frame %u longer than 65535 bytes", i);
     const WaitFor lk(c);
     return host_pipeline(
         c, n,
@@ -1582,7 +1532,7 @@ int bt_parse_filter_ptrs(bt_ctx* c, const uint8_t* const* frames, const uint32_t
 }
 
 int bt_host_stage_bytes(const bt_ctx* c, int with_records, uint32_t* bytes) {
-    if (!c || !bytes) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!c || !bytes) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     std::lock_guard<std::mutex> lk(const_cast<bt_ctx*>(c)->mu);
     *bytes = stage_bytes(c, with_records != 0);
     return BT_OK;
@@ -1590,12 +1540,12 @@ int bt_host_stage_bytes(const bt_ctx* c, int with_records, uint32_t* bytes) {
 
 int bt_host_register(bt_ctx* c, void* host, uint64_t bytes, void** dev_alias) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c || !host || !dev_alias || !bytes) return fail(BT_E_INVALID_ARGUMENT, "null argument / empty range");
+    if (!c || !host || !dev_alias || !bytes) return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty range");
     {
         std::lock_guard<std::mutex> lk(c->mu);
         for (const auto& r : c->host_regs)
             if (r.first == (uintptr_t)host)
-                return fail(BT_E_INVALID_ARGUMENT, "%p is already registered on this context", host);
+                return set_error(BT_E_INVALID_ARGUMENT, "%p is already registered on this context", host);
     }
     // whole pages, in the process's one table (bt_pin.h): a range inside pages another
     // registration holds shares them, one that holds only some of them is refused
@@ -1609,14 +1559,14 @@ int bt_host_register(bt_ctx* c, void* host, uint64_t bytes, void** dev_alias) {
 
 int bt_host_unregister(bt_ctx* c, void* host) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c || !host) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!c || !host) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     uint64_t bytes = 0;
     {
         std::lock_guard<std::mutex> lk(c->mu);
         for (const auto& r : c->host_regs)
             if (r.first == (uintptr_t)host) bytes = r.second;
     }
-    if (!bytes) return fail(BT_E_INVALID_ARGUMENT, "%p is not registered on this context", host);
+    if (!bytes) return set_error(BT_E_INVALID_ARGUMENT, "%p is not registered on this context", host);
     // the last reference waits for every device that holds an alias of the pages (queued
     // kernels that read or write them) before they are unregistered
     if (int rc = bt::pin_release(host, bytes)) return rc;
@@ -1629,7 +1579,7 @@ int bt_host_unregister(bt_ctx* c, void* host) {
 
 int bt_dev_malloc(bt_ctx* c, uint64_t bytes, void** out) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c || !out) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!c || !out) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     static const unsigned flags = [] {
         const char* e = getenv("BT_MALLOC_FLAGS");   // experiments: 4 = hipDeviceMallocContiguous
@@ -1642,7 +1592,7 @@ int bt_dev_malloc(bt_ctx* c, uint64_t bytes, void** out) {
 
 int bt_dev_free(bt_ctx* c, void* p) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
     if (!p) return BT_OK;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipFree(p));   // implicitly waits for the device: no queued kernel still uses p
@@ -1685,8 +1635,8 @@ extern "C" {
 // are ordered after the context's streams (after_cstream) and complete before returning.
 int bt_memcpy_h2d(bt_ctx* c, void* dst, const void* src, uint64_t bytes) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
-    if (bytes && (!dst || !src)) return fail(BT_E_INVALID_ARGUMENT, "null pointer");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
+    if (bytes && (!dst || !src)) return set_error(BT_E_INVALID_ARGUMENT, "null pointer");
     std::lock_guard<std::mutex> lk(c->xfer_mu);
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_xfer(c)) return rc;
@@ -1707,8 +1657,8 @@ int bt_memcpy_h2d(bt_ctx* c, void* dst, const void* src, uint64_t bytes) {
 
 int bt_memcpy_d2h(bt_ctx* c, void* dst, const void* src, uint64_t bytes) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
-    if (bytes && (!dst || !src)) return fail(BT_E_INVALID_ARGUMENT, "null pointer");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
+    if (bytes && (!dst || !src)) return set_error(BT_E_INVALID_ARGUMENT, "null pointer");
     std::lock_guard<std::mutex> lk(c->xfer_mu);
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_xfer(c)) return rc;
@@ -1733,7 +1683,7 @@ int bt_memcpy_d2h(bt_ctx* c, void* dst, const void* src, uint64_t bytes) {
 
 int bt_memset_d(bt_ctx* c, void* dst, int value, uint64_t bytes) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = after_cstream(c)) return rc;
     HIP_TRY(hipMemsetAsync(dst, value, bytes, c->stream));
@@ -1746,9 +1696,9 @@ int bt_ring_walk_tpv3_gpu(bt_ctx* c, const bt_tpv3_ring* ring, const void* ring_
                           uint32_t* n_blocks_taken, uint32_t* bad_dev, void* stream) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
     if (!c || !ring || !ring->base || !ring_dev || !n_desc || !n_blocks_taken || (cap && !desc_dev))
-        return fail(BT_E_INVALID_ARGUMENT, "bt_ring_walk_tpv3_gpu: null argument");
+        return set_error(BT_E_INVALID_ARGUMENT, "bt_ring_walk_tpv3_gpu: null argument");
     if (!ring->n_blocks || ring->block_size < 48 || first_block >= ring->n_blocks)
-        return fail(BT_E_INVALID_ARGUMENT, "bt_ring_walk_tpv3_gpu: bad ring geometry");
+        return set_error(BT_E_INVALID_ARGUMENT, "bt_ring_walk_tpv3_gpu: bad ring geometry");
     *n_desc = 0;
     *n_blocks_taken = 0;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -1778,7 +1728,7 @@ int bt_ring_walk_tpv3_gpu(bt_ctx* c, const bt_tpv3_ring* ring, const void* ring_
         const uint32_t first = *reinterpret_cast<const uint32_t*>(bd + 16);
         if (total + np > cap) break;
         if (np && first >= ring->block_size)
-            return fail(BT_E_INVALID_ARGUMENT, "bt_ring_walk_tpv3_gpu: block %u: first frame outside block", b);
+            return set_error(BT_E_INVALID_ARGUMENT, "bt_ring_walk_tpv3_gpu: block %u: first frame outside block", b);
         w.h[nb++] = RingBlock{b, np, (uint32_t)total, first};
         total += np;
     }
@@ -1790,7 +1740,7 @@ int bt_ring_walk_tpv3_gpu(bt_ctx* c, const bt_tpv3_ring* ring, const void* ring_
     a.desc = desc_dev;
     a.cap = cap;
     a.bad = bad_dev;
-    if (int rc = launch_ring_walk(a, st)) return fail(rc, "ring walk launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (int rc = launch_ring_walk(a, st)) return set_error(rc, "ring walk launch failed: %s", hipGetErrorString(hipGetLastError()));
     HIP_TRY(hipEventRecord(w.done, st));
     w.used = true;
     c->walk_next ^= 1;
@@ -1799,21 +1749,21 @@ int bt_ring_walk_tpv3_gpu(bt_ctx* c, const bt_tpv3_ring* ring, const void* ring_
 #ifdef BT_DEBUG_BOUNDS
     BoundsLog f{};
     if (const uint32_t k = bounds_take_ring(st, &f))
-        return fail(BT_E_INTERNAL, "BT_DEBUG_BOUNDS: ring walk: %u failed checks, first %s index %llu limit %llu", k,
-                    bounds_site_name(f.site), (unsigned long long)f.index, (unsigned long long)f.limit);
+        return set_error(BT_E_INTERNAL, "BT_DEBUG_BOUNDS: ring walk: %u failed checks, first %s index %llu limit %llu", k,
+                         bounds_site_name(f.site), (unsigned long long)f.index, (unsigned long long)f.limit);
 #endif
     return BT_OK;
 }
 
 int bt_host_parallel(bt_ctx* c, void (*fn)(void*, uint32_t, uint32_t), void* user) {
-    if (!c || !fn) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!c || !fn) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     bt::host_parallel(c, [&](unsigned w, unsigned T) { fn(user, w, T); });
     return BT_OK;
 }
 
 int bt_stream_create(bt_ctx* c, void** stream) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c || !stream) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!c || !stream) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -1823,7 +1773,7 @@ int bt_stream_create(bt_ctx* c, void** stream) {
 
 int bt_stream_synchronize(bt_ctx* c, void* stream) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c || !stream) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!c || !stream) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
     return BT_OK;
@@ -1831,7 +1781,7 @@ int bt_stream_synchronize(bt_ctx* c, void* stream) {
 
 int bt_stream_destroy(bt_ctx* c, void* stream) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c || !stream) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!c || !stream) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
     HIP_TRY(hipStreamDestroy(reinterpret_cast<hipStream_t>(stream)));
@@ -1840,7 +1790,7 @@ int bt_stream_destroy(bt_ctx* c, void* stream) {
 
 int bt_synchronize(bt_ctx* c) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->cstream) HIP_TRY(hipStreamSynchronize(c->cstream));
@@ -1854,18 +1804,18 @@ namespace {
 // A bt_field_def table as the kernel takes it (ExTable), with the span and the checks the
 // C-ABI promises. span > 65535 can never parse a frame (lengths are 16-bit): *never = true.
 int build_table(const bt_field_def* f, uint32_t n, ExTable* t, uint64_t* span_out, bool* never) {
-    if (n && !f) return fail(BT_E_INVALID_ARGUMENT, "null field table");
-    if (n > BT_FIELD_MAX) return fail(BT_E_INVALID_ARGUMENT, "%u fields (max %u)", n, BT_FIELD_MAX);
+    if (n && !f) return set_error(BT_E_INVALID_ARGUMENT, "null field table");
+    if (n > BT_FIELD_MAX) return set_error(BT_E_INVALID_ARGUMENT, "%u fields (max %u)", n, BT_FIELD_MAX);
     // getTotalLength (src/parser/FieldDefinition.cpp:31-46): the end of the field that ends
     // last (offset + length in size_t arithmetic)
     uint64_t mo = 0, ml = 0;
     for (uint32_t k = 0; k < n; ++k) {
-        if (f[k].type > BT_FT_CUSTOM) return fail(BT_E_INVALID_ARGUMENT, "field %u: unknown type %u", k, f[k].type);
+        if (f[k].type > BT_FT_CUSTOM) return set_error(BT_E_INVALID_ARGUMENT, "field %u: unknown type %u", k, f[k].type);
         if (f[k].type == BT_FT_BOOLEAN && f[k].length == 0)
-            return fail(BT_E_INVALID_ARGUMENT, "field %u: BOOLEAN of length 0 (the reference reads fieldData[0] "
-                        "of an empty vector)", k);
+            return set_error(BT_E_INVALID_ARGUMENT, "field %u: BOOLEAN of length 0 (the reference reads fieldData[0] "
+                             "of an empty vector)", k);
         if (f[k].offset + f[k].length < f[k].offset)
-            return fail(BT_E_INVALID_ARGUMENT, "field %u: offset + length overflows", k);
+            return set_error(BT_E_INVALID_ARGUMENT, "field %u: offset + length overflows", k);
         if (f[k].offset + f[k].length > mo + ml) { mo = f[k].offset; ml = f[k].length; }
     }
     const uint64_t span = n ? mo + ml : 0;
@@ -1885,43 +1835,29 @@ int build_table(const bt_field_def* f, uint32_t n, ExTable* t, uint64_t* span_ou
 
 int run_extract(bt_ctx* c, const bt_batch* b, const ExTable& t, bool never, const bt_extract_out* o, hipStream_t st,
                 hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-    if (!b || !o) return fail(BT_E_INVALID_ARGUMENT, "null batch/outputs");
-    if (b->n && !b->base) return fail(BT_E_INVALID_ARGUMENT, "null packet buffer");
-    if (!b->desc && b->stride == 0 && b->n) return fail(BT_E_INVALID_ARGUMENT, "fixed-stride mode needs stride > 0");
-    if (o->values && o->n_cap < b->n) return fail(BT_E_INVALID_ARGUMENT, "values n_cap %u < n %u", o->n_cap, b->n);
-    if (b->desc_format > BT_DESC_XDP) return fail(BT_E_INVALID_ARGUMENT, "unknown desc_format %u", b->desc_format);
+    if (!b || !o) return set_error(BT_E_INVALID_ARGUMENT, "null batch/outputs");
+    ExArgs a{};
+    char why[128];
+    const FrameCheck bad = frame_src(b, &a, why, sizeof(why));   // as run_device: the size only for a batch with frames
+    if (bad && bad != kFramesSize) return set_error(BT_E_INVALID_ARGUMENT, "%s", why);
+    if (o->values && o->n_cap < b->n) return set_error(BT_E_INVALID_ARGUMENT, "values n_cap %u < n %u", o->n_cap, b->n);
     if (b->flags & BT_BATCH_LEAN)
-        return fail(BT_E_INVALID_ARGUMENT, "a BT_BATCH_LEAN batch holds frame bytes 12..43 only: no user-table extraction");
+        return set_error(BT_E_INVALID_ARGUMENT, "a BT_BATCH_LEAN batch holds frame bytes 12..43 only: no user-table extraction");
     if (!b->n) return BT_OK;
-    uint64_t bytes = b->bytes;   // as run_device: mandatory with descriptors
-    if (b->desc) {
-        if (!bytes) return fail(BT_E_INVALID_ARGUMENT, "descriptor batch with bytes == 0 (the readable size of base)");
-    } else {
-        const uint64_t need = (uint64_t)b->n * b->stride;
-        if (!bytes) bytes = need;
-        else if (bytes < need) return fail(BT_E_INVALID_ARGUMENT, "fixed-stride batch: bytes %llu < n * stride %llu",
-                                           (unsigned long long)bytes, (unsigned long long)need);
-    }
+    if (bad) return set_error(BT_E_INVALID_ARGUMENT, "%s", why);
     if (never) {   // no frame reaches the span: every packet PACKET_TOO_SHORT, no field
         if (o->status) HIP_TRY(hipMemsetAsync(o->status, 9, b->n, st));
         if (o->values) for (uint32_t k = 0; k < t.n; ++k)
             HIP_TRY(hipMemsetAsync(o->values + (size_t)k * o->n_cap, 0, (size_t)b->n * 8, st));
         return BT_OK;
     }
-    ExArgs a{};
-    a.base = b->base;
-    a.desc = static_cast<const uint64_t*>(b->desc);
-    a.desc_words = b->desc_format == BT_DESC_XDP ? 2u : 1u;
-    a.bytes = read_limit(b->base, bytes);
-    a.stride = b->stride;
-    a.n = b->n;
-    a.ntiles = (b->n + 63) / 64;
+    a.bytes = read_limit(a.base, a.bytes);
     a.status = o->status;
     a.values = o->values;
     a.image = o->image;
     a.n_cap = o->n_cap;
     const int rc = launch_extract(a, t, st, e0, e1);
-    if (rc) return fail(rc, "extract kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return set_error(rc, "extract kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     return check_bounds(st, nullptr, "extract");
 }
 
@@ -1930,7 +1866,7 @@ int run_extract(bt_ctx* c, const bt_batch* b, const ExTable& t, bool never, cons
 extern "C" {
 
 int bt_proto_span(const bt_field_def* fields, uint32_t n_fields, uint64_t* span) {
-    if (!span) return fail(BT_E_INVALID_ARGUMENT, "null span");
+    if (!span) return set_error(BT_E_INVALID_ARGUMENT, "null span");
     ExTable t;
     bool never = false;
     return build_table(fields, n_fields, &t, span, &never);
@@ -1939,7 +1875,7 @@ int bt_proto_span(const bt_field_def* fields, uint32_t n_fields, uint64_t* span)
 int bt_extract_device(bt_ctx* c, const bt_batch* b, const bt_field_def* fields, uint32_t n_fields,
                       const bt_extract_out* out, void* stream) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
     ExTable t;
     bool never = false;
     int rc = build_table(fields, n_fields, &t, nullptr, &never);
@@ -1952,14 +1888,14 @@ int bt_extract_device(bt_ctx* c, const bt_batch* b, const bt_field_def* fields, 
 int bt_time_extract2(bt_ctx* c, const bt_batch* b, const bt_field_def* fields, uint32_t n_fields,
                      const bt_extract_out* out, uint32_t iters, uint32_t mode, bt_timing* t) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c || !b || !out || !iters) return fail(BT_E_INVALID_ARGUMENT, "null argument / zero iterations");
-    if (mode & ~(uint32_t)BT_TIME_KERNEL_EVENTS) return fail(BT_E_INVALID_ARGUMENT, "unknown mode");
+    if (!c || !b || !out || !iters) return set_error(BT_E_INVALID_ARGUMENT, "null argument / zero iterations");
+    if (mode & ~(uint32_t)BT_TIME_KERNEL_EVENTS) return set_error(BT_E_INVALID_ARGUMENT, "unknown mode");
     const bool kev = (mode & BT_TIME_KERNEL_EVENTS) != 0;
     ExTable tab;
     bool never = false;
     int rc = build_table(fields, n_fields, &tab, nullptr, &never);
     if (rc) return rc;
-    if (never || !b->n) return fail(BT_E_INVALID_ARGUMENT, "nothing to time: empty batch or a span no frame reaches");
+    if (never || !b->n) return set_error(BT_E_INVALID_ARGUMENT, "nothing to time: empty batch or a span no frame reaches");
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     if (kev && (rc = ensure_timing_events(c, iters))) return rc;
@@ -2008,7 +1944,7 @@ static uint64_t decode_field_host(const ExField& f, const uint8_t* frame) {
 
 int bt_extract_host(const uint8_t* const* frames, const uint32_t* lens, uint32_t n, const bt_field_def* fields,
                     uint32_t n_fields, uint8_t* status, uint64_t* values, uint8_t* image) {
-    if (n && (!frames || !lens)) return fail(BT_E_INVALID_ARGUMENT, "null frame pointers/lengths");
+    if (n && (!frames || !lens)) return set_error(BT_E_INVALID_ARGUMENT, "null frame pointers/lengths");
     ExTable t;
     bool never = false;
     uint64_t span64 = 0;
@@ -2029,7 +1965,7 @@ int bt_extract_host(const uint8_t* const* frames, const uint32_t* lens, uint32_t
 }
 
 int bt_filter_dfa_pool(const bt_ctx* c, void* out, uint32_t cap, uint32_t* bytes) {
-    if (!c || !bytes || (cap && !out)) return fail(BT_E_INVALID_ARGUMENT, "null argument");
+    if (!c || !bytes || (cap && !out)) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     std::lock_guard<std::mutex> lk(const_cast<bt_ctx*>(c)->mu);
     *bytes = (uint32_t)c->dfa_pool.size();
     if (out && cap) std::memcpy(out, c->dfa_pool.data(), std::min<size_t>(cap, c->dfa_pool.size()));
@@ -2039,8 +1975,8 @@ int bt_filter_dfa_pool(const bt_ctx* c, void* out, uint32_t cap, uint32_t* bytes
 int bt_extract(bt_ctx* c, const uint8_t* const* frames, const uint32_t* lens, uint32_t n, const bt_field_def* fields,
                uint32_t n_fields, uint8_t* status, uint64_t* values, uint8_t* image) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
-    if (!c) return fail(BT_E_INVALID_ARGUMENT, "null context");
-    if (n && (!frames || !lens)) return fail(BT_E_INVALID_ARGUMENT, "null frame pointers/lengths");
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "null context");
+    if (n && (!frames || !lens)) return set_error(BT_E_INVALID_ARGUMENT, "null frame pointers/lengths");
     ExTable t;
     bool never = false;
     uint64_t span64 = 0;
@@ -2109,7 +2045,7 @@ int bt_extract(bt_ctx* c, const uint8_t* const* frames, const uint32_t* lens, ui
             }
         });
         const uint32_t first_bad = *std::min_element(bad.begin(), bad.end());
-        if (first_bad != UINT32_MAX) return fail(BT_E_INVALID_ARGUMENT, "frame %u longer than 65535 bytes", first_bad);
+        if (first_bad != UINT32_MAX) return set_error(BT_E_INVALID_ARGUMENT, "frame %u longer than 65535 bytes", first_bad);
         HIP_TRY(hipMemcpyAsync(c->ex_d, h, in_b, hipMemcpyHostToDevice, c->stream));
         bt_batch b{};
         b.base = c->ex_d;
@@ -2237,7 +2173,7 @@ void bt_record_gather_planes(const void* planes, uint32_t n_cap, uint32_t i, bt_
 
 int bt_record_unpack(bt_ctx* ctx, const void* records, uint32_t n_cap, uint32_t n, uint32_t planes, bt_rec* out,
                      uint64_t* slabs) {
-    if ((!records || (!out && !slabs)) && n) return fail(BT_E_INVALID_ARGUMENT, "null records / out");
+    if ((!records || (!out && !slabs)) && n) return set_error(BT_E_INVALID_ARGUMENT, "null records / out");
     std::atomic<uint64_t> total{0};
     const uint8_t* p = static_cast<const uint8_t*>(records);
     host_parallel(ctx, [&](unsigned w, unsigned T) {

@@ -21,6 +21,8 @@
 #include <thread>
 #include <vector>
 
+#include "beatrice_gpu.h"
+
 namespace {
 
 constexpr uint64_t kBlock = 65536;
@@ -276,7 +278,7 @@ int bt_synth_fill_range(int cfg, uint64_t n, uint64_t seed, const uint64_t* desc
                 const uint64_t a = b * kBlock, e = std::min(hi, a + kBlock);
                 for (uint64_t i = a; i < e; ++i) {
                     const uint64_t d = desc[i];
-                    build(cfg, shape_of(cfg, seed, i), data + ((d & 0xFFFFFFFFFFFFull) - data_off), (uint32_t)(d >> 48),
+                    build(cfg, shape_of(cfg, seed, i), data + (BT_DESC_OFF(d) - data_off), BT_DESC_LEN(d),
                           i, r);
                 }
             }
@@ -325,7 +327,7 @@ uint64_t bt_synth_tpv3_pack(const uint8_t* data, const uint64_t* desc, uint64_t 
         in_blk = 0;
     };
     for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t src = desc[i] & 0xFFFFFFFFFFFFull;
+        const uint64_t src = BT_DESC_OFF(desc[i]);
         const uint32_t len = (uint32_t)(desc[i] >> 48);
         const uint32_t snap = (uint32_t)std::min<uint64_t>(len, max_frame - kMacOff);
         const uint64_t need = (kMacOff + snap + kAlign - 1) & ~(uint64_t)(kAlign - 1);
