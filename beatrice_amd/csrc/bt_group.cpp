@@ -34,10 +34,8 @@
 #include <thread>
 #include <vector>
 
-#include "bt_device.h"
+#include "bt_ctx.h"
 #include "bt_hip_util.h"
-#include "bt_host.h"
-#include "bt_host_pool.h"
 
 namespace {
 
@@ -186,7 +184,7 @@ int run_members(bt_group* g, Fn fn) {
     for (uint32_t k = 0; k < m; ++k)
         if (rc[k]) {
             if (m == 1) return bt::set_error(rc[k], "%s", msg[k].c_str());
-            return bt::set_error(rc[k], "group member %u (device %d): %s", k, bt::ctx_device(g->members[k]),
+            return bt::set_error(rc[k], "group member %u (device %d): %s", k, g->members[k]->device,
                                  msg[k].c_str());
         }
     return BT_OK;
@@ -262,7 +260,7 @@ uint8_t* alias_of(const bt_group* g, uint32_t k, const void* p, uint64_t need) {
 // a registered range is aliases[k], taken on its own device).
 std::vector<int> member_devices(const bt_group* g) {
     std::vector<int> d;
-    for (bt_ctx* c : g->members) d.push_back(bt::ctx_device(c));
+    for (bt_ctx* c : g->members) d.push_back(c->device);
     return d;
 }
 
@@ -415,7 +413,7 @@ static int group_create(const int* devices, uint32_t n_devices, const bt_opts* o
     }
     if (n_devices > 1) {
         std::vector<const cpu_set_t*> pins;
-        for (bt_ctx* c : g->members) pins.push_back(bt::ctx_pin(c));
+        for (bt_ctx* c : g->members) pins.push_back(c->pinned ? &c->pin : nullptr);
         try {
             // each member thread starts on its member's device (every entry point it calls selects
             // the context's device too; this keeps any HIP call made there on the right one)
@@ -457,7 +455,7 @@ int bt_group_filter_compile(bt_group* g, const bt_filter_desc* filters, uint32_t
     try {
         std::unique_lock<std::shared_mutex> lk(g->prog_mu);
         bt::CompiledProgram p;   // compiled once, installed on every device
-        if (int rc = bt::compile_program(filters, n, bt::ctx_flags(g->members[0]), &p)) return rc;
+        if (int rc = bt::compile_program(filters, n, g->members[0]->opts.flags, &p)) return rc;
         const int rc = run_members(g, [&](uint32_t k) { return bt::install_program(g->members[k], p); });
         return rc;
     } catch (const std::exception& e) {
@@ -594,7 +592,7 @@ int bt_group_parse_filter_mapped(bt_group* g, const bt_batch* b, const bt_output
         std::shared_lock<std::shared_mutex> plk(g->prog_mu);
         std::shared_lock<std::shared_mutex> rlk(g->reg_mu);
         const uint32_t m = (uint32_t)g->members.size();
-        const uint32_t flags = bt::ctx_flags(g->members[0]);
+        const uint32_t flags = g->members[0]->opts.flags;
         const bool aos = (flags & BT_OPT_RECORDS_AOS) != 0;
         if (o->records && (flags & BT_OPT_RECORDS_PLANES) && m > 1)
             return bt::set_error(BT_E_INVALID_ARGUMENT, "plane-major records cannot be split across group members");

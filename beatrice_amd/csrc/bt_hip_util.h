@@ -1,5 +1,5 @@
-// bt_hip_util.h — HIP helpers shared by the hipcc-compiled host units (bt_runtime.cpp,
-// bt_group.cpp, bt_pin.cpp).
+// bt_hip_util.h — HIP helpers shared by the hipcc-compiled host units (those that
+// include bt_ctx.h, and bt_pin.cpp).
 #pragma once
 
 #include <hip/hip_runtime_api.h>

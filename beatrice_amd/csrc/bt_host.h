@@ -1,6 +1,8 @@
-// bt_host.h — runtime services shared by the host-only translation units of
-// libbeatrice_gpu.so (bt_ring.cpp, bt_group.cpp): the thread-local error slot behind
-// bt_last_error(), the context's host thread pool, and filter programs.
+// bt_host.h — runtime services shared by every host translation unit of libbeatrice_gpu.so,
+// also those the host compiler builds without HIP (bt_ring.cpp, bt_ring_stage.cpp,
+// bt_format.cpp, bt_records.cpp): the thread-local error slot behind bt_last_error()
+// (bt_context.cpp), the context's host thread pool, and filter programs (bt_program.cpp).
+// The units that see HIP types read the context itself (bt_ctx.h).
 #pragma once
 
 #include <sched.h>
@@ -21,29 +23,17 @@ struct CompiledProgram {
 };
 int compile_program(const bt_filter_desc* f, uint32_t n, uint32_t ctx_flags, CompiledProgram* out);
 int install_program(bt_ctx* c, const CompiledProgram& p);
-uint32_t ctx_flags(const bt_ctx* c);
+// The context's device (for the units that cannot read bt_ctx.h).
 int ctx_device(const bt_ctx* c);
-// The options the context was created with.
-bt_opts ctx_opts(const bt_ctx* c);
-// bt_pcap_filter's staging buffers and streams, kept on the context between calls (bt_pcap.cpp
-// allocates and sizes them; bt_destroy releases them through pcap_stage_free).
-struct PcapStage;
-PcapStage*& ctx_pcap_stage(bt_ctx* c);
-void pcap_stage_free(PcapStage* s);
 // Whether the context's stream still has queued work (hipStreamQuery: not ready).
 bool ctx_stream_busy(bt_ctx* c);
-// The CPUs the context's pool workers are pinned to (its device's NUMA node), or NULL.
-const cpu_set_t* ctx_pin(const bt_ctx* c);
 // Drops the context's cached "is this batch base host memory" answer (after an unregister).
 void ctx_forget_base(bt_ctx* c);
-// bt_host_stage_bytes without the C-ABI's checks.
-uint32_t stage_bytes_of(bt_ctx* c, bool records);
-// Bytes per frame the host pipeline copies to the device (<= stage_bytes_of: a filter-only
-// call stages bytes 12..43 only): the host batches' split cost.
-uint32_t staged_bytes_of(bt_ctx* c, bool records);
-// The same, lock-free: the value the context published when its program was last installed
-// (bt_filter_compile on the context itself or through its group), so a group's split never
-// waits for a member's host batch in flight.
+// Bytes per frame the host pipeline copies to the device (<= bt_host_stage_bytes: a filter-only
+// call stages bytes 12..43 only), the host batches' split cost, lock-free: the value the
+// context published when its program was last installed (bt_filter_compile on the context
+// itself or through its group), so a group's split never waits for a member's host batch in
+// flight.
 uint32_t staged_window(const bt_ctx* c, bool records);
 // CPUs this process may use: its affinity set bounded by the cgroup v2 CPU quota.
 unsigned usable_cpus();

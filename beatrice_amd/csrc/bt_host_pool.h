@@ -1,4 +1,4 @@
-// bt_host_pool.h — the context's host thread pool (beatrice_amd/csrc/bt_runtime.cpp) and a
+// bt_host_pool.h — the context's host thread pool (beatrice_amd/csrc/bt_context.cpp) and a
 // group's member threads (bt_group.cpp), in a header of their own so
 // tests/cpp/test_host_pool.cpp can stress them under ThreadSanitizer on the CPU. Host code only.
 #pragma once
@@ -28,7 +28,7 @@ namespace bt {
 class HostPool {
 public:
     // pin (optional): the CPUs the workers run on, e.g. those of the device's NUMA node
-    // (bt_runtime.cpp place_ctx); the caller, worker 0, stays where it is
+    // (bt_context.cpp place_ctx); the caller, worker 0, stays where it is
     explicit HostPool(unsigned n, const cpu_set_t* pin = nullptr) {
         nthreads_ = n ? (n < 0xFFFFu ? n : 0xFFFFu) : 1;   // indices fit the claim word's 16 bits
         static const bool fixed = getenv("BT_POOL_FIXED") != nullptr;   // A/B: each worker its own index
@@ -54,7 +54,7 @@ public:
     // runs fn(k) for every k in [0, count) and waits; count 0 (or above size()) = size().
     // With count < size() the run's indices are fewer than its threads: the workers that find
     // none left go back to sleep (the context's host pipeline runs a smaller share of the pool
-    // while other callers wait for it, bt_runtime.cpp pipeline_share)
+    // while other callers wait for it, bt_host_batch.cpp pipeline_share)
     void run(const std::function<void(unsigned)>& fn, unsigned count = 0) {
         const unsigned want = count && count < nthreads_ ? count : nthreads_;
         if (want == 1) { fn(0); return; }

@@ -1,5 +1,5 @@
 // bt_pack.h — ordered pack of the selected frames of a batch (bt_pack.hip), shared with the
-// host runtime (bt_pass_pack_device in bt_runtime.cpp).
+// host runtime (bt_pass_pack_device in bt_launch.cpp).
 #pragma once
 
 #include <stdint.h>

@@ -23,8 +23,8 @@ static int set_error(int code, const char*, ...) { return code; }
 #include <mutex>
 #include <vector>
 
+#include "bt_ctx.h"
 #include "bt_hip_util.h"
-#include "bt_host.h"
 #endif
 
 namespace {
@@ -306,7 +306,7 @@ extern "C" int bt_pcap_filter(bt_ctx* c, const uint8_t* file, uint64_t bytes, ui
 
     // chunk capacity: the context's host chunk limits, at most 64 MiB / 1M packets, at least one
     // record of the largest size, and no more than the file can hold
-    const bt_opts o = ctx_opts(c);
+    const bt_opts o = c->opts;
     const uint64_t body = bytes - kGlobalHeader;
     uint64_t cap_bytes = o.host_chunk_bytes ? o.host_chunk_bytes : (64ull << 20);
     cap_bytes = std::min<uint64_t>(cap_bytes, 64ull << 20);
@@ -319,10 +319,10 @@ extern "C" int bt_pcap_filter(bt_ctx* c, const uint8_t* file, uint64_t bytes, ui
     PcapStage* st = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_stage_mu);
-        PcapStage*& slot = ctx_pcap_stage(c);
+        PcapStage*& slot = c->pcap;
         if (!slot) {
             slot = new PcapStage();
-            slot->device = ctx_device(c);
+            slot->device = c->device;
         }
         st = slot;
     }

@@ -1,5 +1,5 @@
 // bt_resume_host.h — the host-only pieces of the two-pass PAYLOAD path: the argument checks of
-// bt_filter_resume_device (bt_runtime.cpp) and the scan of final decision bytes that builds the
+// bt_filter_resume_device (bt_launch.cpp) and the scan of final decision bytes that builds the
 // ring stage's verdict words and counts (bt_ring_stage.cpp). Plain C++ with no device and no
 // runtime state, so tools/resume_host_check.cpp runs both under the host sanitizers.
 #pragma once

@@ -1,0 +1,251 @@
+// bt_timing.cpp — the bench harness (include/beatrice_gpu_bench.h): the bt_time_* entry
+// points, which enqueue K launches between events and report the device's and the host's
+// share of the span.
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+
+#include "bt_ctx.h"
+#include "bt_hip_util.h"
+
+using namespace bt;
+
+// The host side of a timed loop whose launches (K of them, each between the event pair
+// c->timing.tev[2i], c->timing.tev[2i+1]) were enqueued on c->stream after c->timing.ev0 at h0, followed by
+// c->timing.ev1: wait by polling, then fill the breakdown.
+static int finish_timing(bt_ctx* c, uint32_t iters, bool no_kernel_events, std::chrono::steady_clock::time_point h0,
+                         bt_timing* t, const char* who) {
+    using clk = std::chrono::steady_clock;
+    auto ms = [](clk::time_point x, clk::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
+    const auto h1 = clk::now();
+    // Poll instead of hipEventSynchronize: a blocking wait is woken by an interrupt, whose
+    // latency would sit inside the caller's timed region.
+    auto poll = [](hipEvent_t e) -> hipError_t {
+        for (;;) {
+            const hipError_t q = hipEventQuery(e);
+            if (q != hipErrorNotReady) return q;
+        }
+    };
+    HIP_TRY(poll(c->timing.ev0));
+    const auto h2 = clk::now();
+    HIP_TRY(poll(c->timing.ev1));
+    const auto h3 = clk::now();
+    float tot = 0, k = 0, kmin = 1e30f, kmax = 0, lead = 0, gap = 0;
+    HIP_TRY(hipEventElapsedTime(&tot, c->timing.ev0, c->timing.ev1));
+    for (uint32_t i = 0; !no_kernel_events && i < iters; ++i) {
+        float x = 0;
+        HIP_TRY(hipEventElapsedTime(&x, c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+        k += x;
+        kmin = std::min(kmin, x);
+        kmax = std::max(kmax, x);
+        if (i + 1 < iters) {
+            float g = 0;
+            HIP_TRY(hipEventElapsedTime(&g, c->timing.tev[2 * i + 1], c->timing.tev[2 * i + 2]));
+            gap += g;
+        }
+    }
+    if (!no_kernel_events) HIP_TRY(hipEventElapsedTime(&lead, c->timing.ev0, c->timing.tev[0]));
+    const auto h4 = clk::now();
+    if (t) {
+        *t = bt_timing{};
+        t->span_ms = tot;
+        t->main_ms = no_kernel_events ? -1.0f : k / iters;
+        t->main_min_ms = no_kernel_events ? -1.0f : kmin;
+        t->main_max_ms = no_kernel_events ? -1.0f : kmax;
+        t->lead_ms = lead;
+        t->gap_ms = gap;
+        t->enqueue_ms = ms(h0, h1);
+        t->first_seen_ms = ms(h1, h2);
+        t->last_seen_ms = ms(h2, h3);
+        t->query_ms = ms(h3, h4);
+        t->wall_ms = ms(h0, h4);
+        t->spin_rc = c->spin_rc;
+        t->device_flags = c->device_flags;
+    }
+    static const bool dbg = getenv("BT_DEBUG_TIMING") != nullptr;
+    if (dbg)
+        fprintf(stderr, "[%s] enqueue %.3f ms, first-seen %.3f ms, last-seen %.3f ms, queries %.3f ms, "
+                "gpu span %.3f ms\n", who, ms(h0, h1), ms(h1, h2), ms(h2, h3), ms(h3, h4), tot);
+    return BT_OK;
+}
+
+static int ensure_timing_events(bt_ctx* c, uint32_t iters) {
+    while (c->timing.tev.size() < 2 * (size_t)iters) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        c->timing.tev.push_back(e);
+    }
+    return BT_OK;
+}
+
+extern "C" {
+
+int bt_time_pass_pack(bt_ctx* c, const bt_batch* b, const uint64_t* select, const bt_pack_opts* po,
+                      const bt_pack_out* out, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !b || !b->n || !iters || !ms) return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int rc = run_pass_pack(c, b, select, po, out, c->stream, c->timing.tev[2 * i], c->timing.tev[2 * i + 1])) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
+int bt_time_copy_d2d(bt_ctx* c, void* dst, const void* src, uint64_t bytes, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !dst || !src || !bytes || !iters || !ms) return set_error(BT_E_INVALID_ARGUMENT, "null argument / zero size");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i) {
+        HIP_TRY(hipEventRecord(c->timing.tev[2 * i], c->stream));
+        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipEventRecord(c->timing.tev[2 * i + 1], c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
+int bt_time_device2(bt_ctx* c, const bt_batch* b, const bt_outputs* outs, uint32_t n_out, uint32_t iters,
+                    uint32_t mode, bt_timing* t) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !b || !outs || !n_out || !iters) return set_error(BT_E_INVALID_ARGUMENT, "null argument / zero iterations");
+    if (mode & ~(uint32_t)(BT_TIME_KERNEL_EVENTS | BT_TIME_PIPELINED)) return set_error(BT_E_INVALID_ARGUMENT, "unknown mode");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    const bool kev = (mode & BT_TIME_KERNEL_EVENTS) != 0;
+    const bool piped = (mode & BT_TIME_PIPELINED) != 0;
+    if (kev) { if (int rc = ensure_timing_events(c, iters)) return rc; }
+    // BT_OPT_GRAPH: the K steps replay as one hipGraph (no per-kernel events: HIP cannot
+    // time events recorded inside a captured graph), main_ms is then reported as -1.
+    const bool use_graph = (c->opts.flags & BT_OPT_GRAPH) != 0 && !piped;
+    const bt_outputs* o = outs;
+    const bool cached = c->tgraph.exec && c->tgraph.iters == iters && !std::memcmp(&c->tgraph.batch, b, sizeof(*b)) &&
+                        !std::memcmp(&c->tgraph.out, o, sizeof(*o));
+    if (use_graph && !cached) {
+        // Build once (the first call is the caller's untimed warm-up): the main kernel +
+        // the compaction kernels, K times, in one graph.
+        if (c->tgraph.exec) { (void)hipGraphExecDestroy(c->tgraph.exec); c->tgraph.exec = nullptr; }
+        if (o->pass_idx || o->n_pass) { int rc = ensure_ws(c, b->n); if (rc) return rc; }
+        hipGraph_t g = nullptr;
+        HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
+        int rc = BT_OK;
+        for (uint32_t i = 0; rc == BT_OK && i < iters; ++i) rc = run_device(c, b, o, c->stream, false, nullptr, nullptr);
+        hipError_t ee = hipStreamEndCapture(c->stream, &g);
+        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+        if (ee != hipSuccess || !g) return set_error(BT_E_INTERNAL, "graph capture failed: %s", hipGetErrorString(ee));
+        hipError_t e = hipGraphInstantiate(&c->tgraph.exec, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        if (e != hipSuccess) { c->tgraph.exec = nullptr; return set_error(BT_E_INTERNAL, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
+        c->tgraph.batch = *b;
+        c->tgraph.out = *o;
+        c->tgraph.iters = iters;
+    }
+    if (piped) {
+        if (int rc = ensure_cstream(c)) return rc;
+        if (!c->timing.pipe_done) HIP_TRY(hipEventCreateWithFlags(&c->timing.pipe_done, hipEventDisableTiming));
+        if (!c->timing.pipe_step) HIP_TRY(hipEventCreateWithFlags(&c->timing.pipe_step, hipEventDisableTiming));
+    }
+    const auto h0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipEventRecord(c->timing.ev0, c->stream));
+    if (use_graph) {
+        HIP_TRY(hipGraphLaunch(c->tgraph.exec, c->stream));
+    } else {
+        // Step i uses output set i % n_out. Pipelined (bt_parse_filter_device_async per
+        // step): each compaction runs beside the next step's main kernel and the last one
+        // joins c->stream before the closing event. The per-kernel event pairs
+        // (BT_TIME_KERNEL_EVENTS) are recorded by the main kernel's own dispatch; they cost
+        // the GPU ~9 us per launch on gfx950 (tools/calib/boundary.hip), so the bench
+        // times its steps without them and measures the kernel in a second pass.
+        // With one output set, step i + 1's main kernel would rewrite the verdict words
+        // step i's compaction reads: it waits for that compaction (no overlap, no race).
+        const bool serial = piped && n_out == 1;
+        for (uint32_t i = 0; i < iters; ++i) {
+            const bt_outputs* oi = outs + (i % n_out);
+            hipEvent_t e0 = kev ? c->timing.tev[2 * i] : nullptr, e1 = kev ? c->timing.tev[2 * i + 1] : nullptr;
+            if (serial && i) HIP_TRY(hipStreamWaitEvent(c->stream, c->timing.pipe_step, 0));
+            int rc = piped ? run_device(c, b, oi, c->stream, false, e0, e1, c->ws.cstream,
+                                        i + 1 == iters ? c->timing.pipe_done : serial ? c->timing.pipe_step : nullptr)
+                           : run_device(c, b, oi, c->stream, false, e0, e1);
+            if (rc) return rc;
+        }
+        if (piped) HIP_TRY(hipStreamWaitEvent(c->stream, c->timing.pipe_done, 0));
+    }
+    HIP_TRY(hipEventRecord(c->timing.ev1, c->stream));
+    return finish_timing(c, iters, use_graph || !kev, h0, t, "bt_time_device");
+}
+
+int bt_time_device_ex(bt_ctx* c, const bt_batch* b, const bt_outputs* o, uint32_t iters, bt_timing* t) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    const uint32_t mode = BT_TIME_KERNEL_EVENTS | ((c && (c->opts.flags & BT_OPT_PIPELINE)) ? BT_TIME_PIPELINED : 0u);
+    return bt_time_device2(c, b, o, 1, iters, mode, t);
+}
+
+int bt_time_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, uint32_t iters, float* ms_per_iter,
+                   float* main_ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    bt_timing t{};
+    const int rc = bt_time_device_ex(c, b, o, iters, &t);
+    if (rc) return rc;
+    if (ms_per_iter) *ms_per_iter = t.span_ms / iters;
+    if (main_ms) *main_ms = t.main_ms;
+    return BT_OK;
+}
+
+int bt_time_extract2(bt_ctx* c, const bt_batch* b, const bt_field_def* fields, uint32_t n_fields,
+                     const bt_extract_out* out, uint32_t iters, uint32_t mode, bt_timing* t) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !b || !out || !iters) return set_error(BT_E_INVALID_ARGUMENT, "null argument / zero iterations");
+    if (mode & ~(uint32_t)BT_TIME_KERNEL_EVENTS) return set_error(BT_E_INVALID_ARGUMENT, "unknown mode");
+    const bool kev = (mode & BT_TIME_KERNEL_EVENTS) != 0;
+    ExTable tab;
+    bool never = false;
+    int rc = build_table(fields, n_fields, &tab, nullptr, &never);
+    if (rc) return rc;
+    if (never || !b->n) return set_error(BT_E_INVALID_ARGUMENT, "nothing to time: empty batch or a span no frame reaches");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (kev && (rc = ensure_timing_events(c, iters))) return rc;
+    const auto h0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipEventRecord(c->timing.ev0, c->stream));
+    for (uint32_t i = 0; i < iters; ++i)
+        if ((rc = run_extract(c, b, tab, never, out, c->stream, kev ? c->timing.tev[2 * i] : nullptr,
+                              kev ? c->timing.tev[2 * i + 1] : nullptr)))
+            return rc;
+    HIP_TRY(hipEventRecord(c->timing.ev1, c->stream));
+    return finish_timing(c, iters, !kev, h0, t, "bt_time_extract");
+}
+
+int bt_time_extract_ex(bt_ctx* c, const bt_batch* b, const bt_field_def* fields, uint32_t n_fields,
+                       const bt_extract_out* out, uint32_t iters, bt_timing* t) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    return bt_time_extract2(c, b, fields, n_fields, out, iters, BT_TIME_KERNEL_EVENTS, t);
+}
+
+}  // extern "C"
+
+namespace bt {
+
+void release_timing_graph(bt_ctx* c) {
+    if (c->tgraph.exec) (void)hipGraphExecDestroy(c->tgraph.exec);
+}
+
+void release_timing(bt_ctx* c) {
+    if (c->timing.pipe_step) (void)hipEventDestroy(c->timing.pipe_step);
+    for (auto e : c->timing.tev) (void)hipEventDestroy(e);
+    if (c->timing.pipe_done) (void)hipEventDestroy(c->timing.pipe_done);
+    if (c->timing.ev0) (void)hipEventDestroy(c->timing.ev0);
+    if (c->timing.ev1) (void)hipEventDestroy(c->timing.ev1);
+}
+
+}  // namespace bt
