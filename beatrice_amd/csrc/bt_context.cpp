@@ -213,8 +213,8 @@ int bt_create(int device, const bt_opts* opts, bt_ctx** out) {
     (void)hipGetDeviceFlags(&c->device_flags);
     (void)hipEventCreate(&c->timing.ev0);
     (void)hipEventCreate(&c->timing.ev1);
-    c->grid = c->opts.grid_waves ? (int)((c->opts.grid_waves + kWavesPerBlock - 1) / kWavesPerBlock)
-                                 : device_grid_blocks(device);
+    // 0: one residency wave of whichever kernel variant a call launches (resident_grid)
+    c->grid = c->opts.grid_waves ? (int)((c->opts.grid_waves + kWavesPerBlock - 1) / kWavesPerBlock) : 0;
     to_device_program(nullptr, 0, &c->prog);
     bt::publish_staged_window(c);
     place_ctx(c);

@@ -81,7 +81,6 @@ int launch_main(const MainArgs& a, const DevProgram& prog, int rec_layout, bool 
 // of workspace.
 int launch_compact(const uint64_t* verdict, uint32_t n, uint32_t* chunk_sums, uint32_t* pass_idx,
                    uint32_t* n_pass, void* stream);
-int device_grid_blocks(int device);
 
 // ---- second pass of the PAYLOAD filter over a prefix batch (bt_payload_resume.hip) ----
 // One batch of n WHOLE frames and the first pass's decision bytes, rewritten in place where the

@@ -22,14 +22,12 @@
 // Fields that end past the staged window (span > 256) read their bytes from memory
 // directly, and so does the image then (a byte per lane and store). Both forms give
 // identical results; tests check both (tests/test_gpu_extract.py).
-#include <hip/hip_ext.h>
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <map>
-#include <mutex>
+#include <atomic>
 
+#include "bt_dev_util.h"
 #include "bt_device.h"
+#include "bt_hip_launch.h"
 
 namespace bt {
 
@@ -41,9 +39,8 @@ namespace {
 // Header loads and the value / image stores are non-temporal: nothing re-reads them, and
 // with the default policy c1 took 0.383-0.386 ms against 0.362 (nt loads alone 0.392-0.394,
 // nt stores alone 0.374-0.377; profiles/r02/ab/extract_policy.txt).
-typedef unsigned int ex_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld16_nt(const uint8_t* p) {
-    const ex_u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const ex_u32x4*>(p));
+    const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
     return make_uint4(x.x, x.y, x.z, x.w);
 }
 template <class T>
@@ -170,9 +167,7 @@ __global__ __launch_bounds__(kBlock) void bt_extract_tile(ExArgs a, ExTable tab)
         }
         meta[lane] = s | (ok ? 0x100u : 0u);
         offs[lane] = off;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 
         // ---- DECODE: one u64 per numeric field per packet, field-major ----
         const uint8_t* frame = a.base + off;
@@ -229,31 +224,13 @@ __global__ __launch_bounds__(kBlock) void bt_extract_tile(ExArgs a, ExTable tab)
                     out[q] = (uint8_t)val;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
 }
 
 }  // namespace
 
-uint32_t bounds_take_extract(void* stream, BoundsLog* first) {
-#ifdef BT_DEBUG_BOUNDS
-    if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return 0;
-    BoundsLog log{};
-    if (hipMemcpyFromSymbol(&log, HIP_SYMBOL(g_bounds_extract), sizeof(log)) != hipSuccess) return 0;
-    if (log.count) {
-        const BoundsLog zero{};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_extract), &zero, sizeof(zero));
-        if (first) *first = log;
-    }
-    return log.count;
-#else
-    (void)stream;
-    (void)first;
-    return 0;
-#endif
-}
+uint32_t bounds_take_extract(void* stream, BoundsLog* first) { return bounds_take(g_bounds_extract, stream, first); }
 
 #ifndef BT_EX_BLOCKS_PER_CU
 #define BT_EX_BLOCKS_PER_CU 4   // grid cap (blocks per CU), a build knob for A/B
@@ -265,32 +242,14 @@ int launch_extract(const ExArgs& a, const ExTable& tab_in, void* stream, void* t
     // windows read at its end; odd, so the per-lane reads spread over the banks
     tab.row_dw = 4u * ((tab.window + 15u + 15u) / 16u) + 3u;
     const uint32_t dyn = (uint32_t)sizeof(uint32_t) * kWavesPerBlock * (kWave * tab.row_dw + 3u * kWave);
-    static int cus = 0;
-    static std::map<uint32_t, int> per_cu_of;   // resident blocks per CU, by LDS size
-    static std::mutex mu;
-    int per_cu = 1;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!cus) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                cus = prop.multiProcessorCount;
-            if (cus <= 0) cus = 256;
-        }
-        auto it = per_cu_of.find(dyn);
-        if (it == per_cu_of.end()) {
-            // the widest window (256 B) needs 74 KiB per block: past the 64-KiB default
-            if (dyn > 65536u &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&bt_extract_tile),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess)
-                return BT_E_INTERNAL;
-            int r = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, bt_extract_tile, kBlock, dyn) != hipSuccess || r <= 0)
-                r = 1;
-            it = per_cu_of.emplace(dyn, r).first;
-        }
-        per_cu = it->second;
+    // the widest window (256 B) needs 74 KiB per block: past the 64-KiB default, which is raised
+    // (never lowered) before the first occupancy query and launch at that size
+    static std::atomic<uint32_t> lds_limit{65536u};
+    if (dyn > lds_limit.load()) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&bt_extract_tile),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess)
+            return BT_E_INTERNAL;
+        lds_limit.store(dyn);
     }
     // With the non-temporal policy, at most 4 blocks (16 waves) per CU: c1 0.333-0.355 ms
     // against 0.351-0.360 at 5 and 0.380-0.385 at 3 (profiles/r02/ab/extract_policy.txt).
@@ -298,15 +257,11 @@ int launch_extract(const ExArgs& a, const ExTable& tab_in, void* stream, void* t
     // and fewer concurrent read/write streams suit HBM better (c1, 16M packets: 0.432 ms
     // at 8 blocks/CU, 0.383-0.393 at 4, 0.383-0.385 at 5, 0.387-0.389 at 6, 0.425-0.437
     // at 3, 0.529-0.541 at 2; alternating processes, profiles/r02/ab/c1_grid.txt).
-    per_cu = std::min(per_cu, BT_EX_BLOCKS_PER_CU);
+    const int resident = std::min(resident_grid<bt_extract_tile>(dyn), BT_EX_BLOCKS_PER_CU * cu_count());
     const uint32_t needed = (a.ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const uint32_t grid = std::min<uint32_t>(needed, (uint32_t)(cus * per_cu));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipEvent_t e0 = reinterpret_cast<hipEvent_t>(timing_start), e1 = reinterpret_cast<hipEvent_t>(timing_stop);
-    if (e0 || e1)   // timed from the kernel's own dispatch packet (as launch_main)
-        hipExtLaunchKernelGGL(bt_extract_tile, dim3(grid), dim3(kBlock), dyn, st, e0, e1, 0, a, tab);
-    else
-        hipLaunchKernelGGL(bt_extract_tile, dim3(grid), dim3(kBlock), dyn, st, a, tab);
+    const uint32_t grid = std::min<uint32_t>(needed, (uint32_t)resident);
+    launch(bt_extract_tile, dim3(grid), dim3(kBlock), dyn, reinterpret_cast<hipStream_t>(stream),
+           reinterpret_cast<hipEvent_t>(timing_start), reinterpret_cast<hipEvent_t>(timing_stop), a, tab);
     return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
 }
 

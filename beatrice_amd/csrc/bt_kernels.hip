@@ -24,15 +24,13 @@
 // comment above it); bt_parse_filter_main serves fixed stride and the other layouts.
 // Replaces the per-packet work of reference src/parser/ProtocolParser.cpp:238-433 and
 // src/PacketFilter.cpp:57-372 (see DESIGN.md for the line-by-line mapping).
-#include <hip/hip_ext.h>
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
 
+#include "bt_dev_util.h"
 #include "bt_device.h"
+#include "bt_hip_launch.h"
 #include "bt_payload_walk.h"
 #include "bt_slot_eval.h"
 
@@ -47,30 +45,7 @@ __device__ __forceinline__ uint32_t be32_of(const uint32_t* w, int i) {
     return (byte_of(w, i) << 24) | (byte_of(w, i + 1) << 16) | (byte_of(w, i + 2) << 8) | byte_of(w, i + 3);
 }
 
-// K little-endian dwords starting at byte `a` of the LDS image (any alignment).
-template <int K>
-__device__ __forceinline__ void window(const uint32_t* lds, uint32_t a, uint32_t* out) {
-    const uint32_t d = a >> 2, sh = a & 3u;
-    uint32_t prev = lds[d];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        uint32_t next = lds[d + k + 1];
-        out[k] = __builtin_amdgcn_alignbyte(next, prev, sh);
-        prev = next;
-    }
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-    // Lanes of one wavefront hand rows to each other through LDS: keep the compiler
-    // from moving LDS accesses across this point and drain the LDS queue.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ bool is_vlan(uint32_t et) { return et == 0x8100u || et == 0x88A8u; }
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // 16-B global load / store; `nt` selects the non-temporal (streaming) cache policy.
 __device__ __forceinline__ uint4 ld16(const uint8_t* p, bool nt) {
@@ -647,10 +622,22 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p, uint32_
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
 }
 
+// The kernel variants launch_t can launch; no other combination of template arguments compiles.
+// filter: 0 none, 1 built-in slots only, 2 with PAYLOAD slots; without records there is a filter.
+// bt_parse_filter_main prefetches the next tile only in descriptor mode (fixed strides lost
+// 16 % on C2 with it) and not for PAYLOAD programs (main_waves_per_eu); bt_parse_filter_pipe
+// serves descriptor mode with tiled records or none, never PAYLOAD programs (launch_t).
+constexpr bool main_variant(int fixed_log2, int rec, int filter, bool prefetch) {
+    return (rec != kRecNone || filter != 0) && (!prefetch || (fixed_log2 < 0 && filter != 2));
+}
+constexpr bool pipe_variant(int rec, int filter, int dw) {
+    return (rec == kRecTiled || (rec == kRecNone && filter != 0)) && filter != 2 && (dw == 1 || dw == 2);
+}
+
 // Whether bt_parse_filter_main issues the next tile's loads after the record stores (see
 // the kernel); launch_t sizes the grid by it.
-constexpr bool late_issue(int fixed_log2, int rec, int filter, bool prefetch) {
-    return fixed_log2 >= 0 && !prefetch && rec != kRecAoS && filter == 1;
+constexpr bool late_issue(int fixed_log2, int rec, int filter) {
+    return fixed_log2 >= 0 && rec != kRecAoS && filter == 1;
 }
 
 // Waves per SIMD the compiler must fit bt_parse_filter_main into (1: no constraint). PAYLOAD
@@ -660,13 +647,45 @@ constexpr bool late_issue(int fixed_log2, int rec, int filter, bool prefetch) {
 // with /GET|POST/ last 0.773-0.777 against 0.912-0.916; tools/gpu_payload_libs.sh,
 // profiles/r06/payload/libs_wpe4.log). launch_t runs those programs without the next-tile
 // prefetch, whose registers would spill at 128 (as would AoS records').
-constexpr int main_waves_per_eu(int fixed_log2, int rec, int filter, bool prefetch) {
-    return fixed_log2 < 0 && filter == 2 && !prefetch && rec != kRecAoS ? 4 : 1;
+constexpr int main_waves_per_eu(int fixed_log2, int rec, int filter) {
+    return fixed_log2 < 0 && filter == 2 && rec != kRecAoS ? 4 : 1;
+}
+
+// Tile order: cyclic (wave w takes w, w+W, ...) or blocked (wave w takes one contiguous
+// range, so concurrent accesses spread over the whole buffer). Wave `wid` of the block takes
+// tiles t, t + step, ... below t_end (none when t >= t_end).
+struct TileRange {
+    uint32_t t, t_end, step;
+};
+__device__ __forceinline__ TileRange tile_range(const MainArgs& a, uint32_t wid) {
+    const uint32_t total_waves = gridDim.x * kWavesPerBlock;
+    const uint32_t gw = blockIdx.x * kWavesPerBlock + wid;
+    if (a.blocked) {
+        const uint32_t per = (a.ntiles + total_waves - 1) / total_waves;
+        return {gw * per, min(a.ntiles, gw * per + per), 1u};
+    }
+    return {gw, a.ntiles, total_waves};
+}
+
+// Tile t's decision bytes and verdict word as two unconditional buffer stores, so that a wait
+// behind them counts the same operations on every path: a lane past n, a null output and a
+// lane other than 0 of the verdict store get an empty range or an offset past it, which the
+// hardware drops.
+__device__ __forceinline__ void store_counted(const MainArgs& a, uint32_t t, uint32_t p0, uint32_t lane, uint32_t code,
+                                              uint32_t slot, uint64_t pass) {
+    const uint32_t cnt = min(64u, a.n - p0);
+    const auto rd = rsrc_of(a.decide ? a.decide + p0 : nullptr, a.decide ? cnt : 0u);
+    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)((code << 6) | slot), rd, (int)lane, 0, 0);
+    const bool v_in = BT_IN(&g_bounds_main, kSiteVerdict, t, a.ntiles);
+    const auto rv = rsrc_of(a.verdict ? a.verdict + t : nullptr, a.verdict && v_in ? 8u : 0u);
+    const u32x2 pv = {(uint32_t)pass, (uint32_t)(pass >> 32)};
+    __builtin_amdgcn_raw_buffer_store_b64(pv, rv, lane == 0 ? 0 : (int)kOob, 0, 0);
 }
 
 template <int FIXED_LOG2, int REC, int FILTER, bool PREFETCH>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(main_waves_per_eu(FIXED_LOG2, REC, FILTER, PREFETCH))))
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(main_waves_per_eu(FIXED_LOG2, REC, FILTER))))
 void bt_parse_filter_main(MainArgs a, DevProgram prog) {
+    static_assert(main_variant(FIXED_LOG2, REC, FILTER, PREFETCH), "a variant launch_t never launches");
     // Per-wave LDS image: 64 rows x 33 dwords.
     constexpr uint32_t kRow = row_dw<FIXED_LOG2>();
     // a wave's image; with AoS records at least the tile's 6 KiB of bt_rec (staged below)
@@ -677,30 +696,12 @@ void bt_parse_filter_main(MainArgs a, DevProgram prog) {
     const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform
     uint32_t* img = lds_all + wid * kImg;
     const uint32_t* row = img + lane * kRow;
-    if (FILTER == 2 && a.dfa_bytes) {   // uniform: the whole block copies the pool once
-        const uint4* src = reinterpret_cast<const uint4*>(a.dfa);
-        for (uint32_t k = threadIdx.x; k < (a.dfa_bytes + 15u) / 16u && BT_IN(&g_bounds_main, kSitePayload, 16u * k, kDfaPoolMax); k += kBlock)
-            dyn_lds[k] = src[k];
-        __syncthreads();
-    }
+    if (FILTER == 2 && a.dfa_bytes) copy_dfa_pool(dyn_lds, a.dfa, a.dfa_bytes, &g_bounds_main);   // uniform
     const uint8_t* dfa_lds = reinterpret_cast<const uint8_t*>(dyn_lds);
 
-    const uint32_t total_waves = gridDim.x * kWavesPerBlock;
-
-    // Tile order: cyclic (wave w takes w, w+W, ...) or blocked (wave w takes one
-    // contiguous range, so concurrent accesses spread over the whole buffer).
-    const uint32_t gw = blockIdx.x * kWavesPerBlock + wid;
-    uint32_t t, t_end, step;
-    if (a.blocked) {
-        const uint32_t per = (a.ntiles + total_waves - 1) / total_waves;
-        t = gw * per;
-        t_end = min(a.ntiles, t + per);
-        step = 1;
-    } else {
-        t = gw;
-        t_end = a.ntiles;
-        step = total_waves;
-    }
+    const TileRange tiles = tile_range(a, wid);
+    const uint32_t t_end = tiles.t_end, step = tiles.step;
+    uint32_t t = tiles.t;
     const uint32_t need_max = REC != kRecNone ? kNeedParse : kNeedFilter;
     const HotProgram hot = hot_program(prog);
     bool wide = false;   // wave-uniform: previous tile mostly needed chunks 4..7
@@ -715,14 +716,13 @@ void bt_parse_filter_main(MainArgs a, DevProgram prog) {
     // whose staging loads would have to wait behind the next tile's loads, and not
     // parse-only (nothing to overlap: C2 0.321 against 0.319 ms). Its header loads are
     // always non-temporal (BT_OPT_CACHE_DEFAULT keeps the default policy for the rest).
-    constexpr bool LATE = late_issue(FIXED_LOG2, REC, FILTER, PREFETCH);
+    constexpr bool LATE = late_issue(FIXED_LOG2, REC, FILTER);
     if ((PREFETCH || LATE) && t < t_end) issue_loads<FIXED_LOG2, LATE>(a, t, lane, st, wide, need_max);
-    if (LATE && FILTER && t < t_end) {
+    if (LATE && t < t_end) {
         // stand-ins for a tile's decision / verdict stores (an empty range: dropped), so
         // the loop top's wait counts the same operations on the first iteration as later
         const auto r = rsrc_of(g_zero16, 0u);
         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, r, 0, 0, 0);
-        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
         const u32x2 z = {0u, 0u};
         __builtin_amdgcn_raw_buffer_store_b64(z, r, 16, 0, 0);
     }
@@ -816,15 +816,8 @@ void bt_parse_filter_main(MainArgs a, DevProgram prog) {
             const uint32_t code = filter_packet<FILTER>(a, prog, hot, dfa_lds, img + lane * kRow, kRow, my_off, len, w0, live,
                                                         slot, reuse);
             const uint64_t pass = __ballot(live && code == BT_DECIDE_PASS);
-            if (LATE) {   // unconditional buffer stores: a static count behind the next loads
-                const uint32_t cnt = min(64u, a.n - p0);
-                const auto rd = rsrc_of(a.decide ? a.decide + p0 : nullptr, a.decide ? cnt : 0u);
-                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)((code << 6) | slot), rd, (int)lane, 0, 0);
-                const bool v_in = BT_IN(&g_bounds_main, kSiteVerdict, t, a.ntiles);
-                const auto rv = rsrc_of(a.verdict ? a.verdict + t : nullptr, a.verdict && v_in ? 8u : 0u);
-                typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                const u32x2 pv = {(uint32_t)pass, (uint32_t)(pass >> 32)};
-                __builtin_amdgcn_raw_buffer_store_b64(pv, rv, lane == 0 ? 0 : (int)kOob, 0, 0);
+            if (LATE) {   // a static count behind the next loads
+                store_counted(a, t, p0, lane, code, slot, pass);
             } else {
                 if (a.decide && live && BT_IN(&g_bounds_main, kSiteDecide, my, a.n)) a.decide[my] = (uint8_t)((code << 6) | slot);
                 if (lane == 0 && a.verdict && BT_IN(&g_bounds_main, kSiteVerdict, t, a.ntiles))
@@ -904,7 +897,6 @@ __device__ __forceinline__ void load_desc_pipe(const MainArgs& a, uint32_t t, bo
     const auto r = rsrc_of(a.desc + (valid ? (uint64_t)DW * p0 : 0ull), cnt * 8u * DW);
     const uint32_t qoff = (lane >> 2) * 8u * DW;
     if constexpr (DW == 1) {
-        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
         const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)(lane * 8u), 0, BT_DESC_AUX);
         d.me[0] = v.x; d.me[1] = v.y;
 #pragma unroll
@@ -931,9 +923,11 @@ __device__ __forceinline__ void decode_desc(const uint32_t (&w)[DW + 1], uint64_
     else desc_xdp(d, w[2], off, len);
 }
 
-// Round A of tile t from descriptors already in registers (issue_loads' loads, with the
-// zero line standing in for the skipped ones). A packet past n has an all-zero
-// descriptor: off = len = 0, so nothing of it is read.
+// Round A of tile t from descriptors already in registers: the chunks issue_loads' descriptor
+// branch reads, by the same predicate (keep the two in step; one shared function changed the
+// code of every descriptor-mode bt_parse_filter_main, CHANGELOG.md), with the zero line standing
+// in for the skipped ones. A packet past n has an all-zero descriptor: off = len = 0, so
+// nothing of it is read.
 template <int DW>
 __device__ __forceinline__ void issue_round_a_pipe(const MainArgs& a, uint32_t lane, const TileDesc<DW>& d,
                                                    Stage<-1>& st, bool wide, uint32_t need_max) {
@@ -991,35 +985,18 @@ __device__ __forceinline__ void pad_stores() {   // the prologue's stand-ins for
 // cost more HBM efficiency than the hidden latency gains.
 template <int REC, int FILTER, int DW>
 __global__ __launch_bounds__(kBlock) void bt_parse_filter_pipe(MainArgs a, DevProgram prog) {
-    static_assert(REC == kRecTiled || REC == kRecNone, "pipe variant: tiled records or none");
+    static_assert(pipe_variant(REC, FILTER, DW), "a variant launch_t never launches");
+    static_assert(FILTER != 2, "PAYLOAD programs run in bt_parse_filter_main");
     constexpr uint32_t kRow = kRowDwords;
     __shared__ uint32_t lds_all[kWavesPerBlock * kWave * kRow + 32];   // + tail pad for over-reads
-    extern __shared__ uint4 dyn_lds[];   // PAYLOAD DFA pool (a.dfa_bytes), else empty
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform
     uint32_t* img = lds_all + wid * (kWave * kRow);
     const uint32_t* row = img + lane * kRow;
-    if (FILTER == 2 && a.dfa_bytes) {
-        const uint4* src = reinterpret_cast<const uint4*>(a.dfa);
-        for (uint32_t k = threadIdx.x; k < (a.dfa_bytes + 15u) / 16u && BT_IN(&g_bounds_main, kSitePayload, 16u * k, kDfaPoolMax); k += kBlock)
-            dyn_lds[k] = src[k];
-        __syncthreads();
-    }
-    const uint8_t* dfa_lds = reinterpret_cast<const uint8_t*>(dyn_lds);
 
-    const uint32_t total_waves = gridDim.x * kWavesPerBlock;
-    const uint32_t gw = blockIdx.x * kWavesPerBlock + wid;
-    uint32_t t, t_end, step;
-    if (a.blocked) {
-        const uint32_t per = (a.ntiles + total_waves - 1) / total_waves;
-        t = gw * per;
-        t_end = min(a.ntiles, t + per);
-        step = 1;
-    } else {
-        t = gw;
-        t_end = a.ntiles;
-        step = total_waves;
-    }
+    const TileRange tiles = tile_range(a, wid);
+    const uint32_t t_end = tiles.t_end, step = tiles.step;
+    uint32_t t = tiles.t;
     if (t >= t_end) return;   // wave-uniform; no block barrier follows
     const uint32_t need_max = REC != kRecNone ? kNeedParse : kNeedFilter;
     const HotProgram hot = hot_program(prog);
@@ -1080,16 +1057,9 @@ __global__ __launch_bounds__(kBlock) void bt_parse_filter_pipe(MainArgs a, DevPr
         // ---- FILTER ----
         if (FILTER) {
             uint32_t slot;
-            const uint32_t code = filter_packet<FILTER>(a, prog, hot, dfa_lds, img + lane * kRow, kRow, my_off, len, w0, live, slot);
-            const uint64_t pass = __ballot(live && code == BT_DECIDE_PASS);
-            const uint32_t cnt = min(64u, a.n - p0);
-            const auto rd = rsrc_of(a.decide ? a.decide + p0 : nullptr, a.decide ? cnt : 0u);
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)((code << 6) | slot), rd, (int)lane, 0, 0);
-            const bool v_in = BT_IN(&g_bounds_main, kSiteVerdict, t, a.ntiles);
-            const auto rv = rsrc_of(a.verdict ? a.verdict + t : nullptr, a.verdict && v_in ? 8u : 0u);
-            typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-            const u32x2 pv = {(uint32_t)pass, (uint32_t)(pass >> 32)};
-            __builtin_amdgcn_raw_buffer_store_b64(pv, rv, lane == 0 ? 0 : (int)kOob, 0, 0);
+            // no PAYLOAD slot stages a window here: no DFA pool, and the row is not written
+            const uint32_t code = filter_packet<FILTER>(a, prog, hot, nullptr, img + lane * kRow, kRow, my_off, len, w0, live, slot);
+            store_counted(a, t, p0, lane, code, slot, __ballot(live && code == BT_DECIDE_PASS));
         }
 
         wave_lds_sync();   // this tile's LDS reads are done
@@ -1180,46 +1150,6 @@ __global__ __launch_bounds__(256) void bt_compact(const uint64_t* verdict, const
     }
 }
 
-int cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                  ? prop.multiProcessorCount : 256;
-    }
-    return cus;
-}
-
-// One residency wave of blocks: the persistent grid-stride loop then has no tail of
-// late blocks (measured: 2x residency cost C3 11 %). Cached per kernel instantiation
-// (the template argument), and for PAYLOAD programs per dynamic-LDS size.
-template <auto Kernel>
-int resident_grid(uint32_t dyn) {
-    static int blocks = 0;
-    static uint32_t last_dyn = ~0u;
-    static int last_blocks = 0;
-    static std::mutex mu;
-    auto query = [&](uint32_t bytes) {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kernel, kBlock, bytes) != hipSuccess || per_cu < 1)
-            return 1024;
-        return prop.multiProcessorCount * per_cu;
-    };
-    std::lock_guard<std::mutex> lk(mu);
-    if (dyn) {   // a PAYLOAD program: occupancy depends on its DFA pool size
-        if (dyn != last_dyn) {
-            last_blocks = query(dyn);
-            last_dyn = dyn;
-        }
-        return last_blocks;
-    }
-    if (!blocks) blocks = query(0);
-    return blocks;
-}
-
 // The counted-wait pipeline (bt_parse_filter_pipe) serves descriptor mode with tiled
 // records or none; BT_NO_PIPE=1 in the environment selects bt_parse_filter_main
 // instead (A/B).
@@ -1231,74 +1161,77 @@ bool use_pipe() {
     return on;
 }
 
+// One launch of the variant `Kernel`: `grid` blocks when the caller fixed it (> 0); else
+// `auto_grid` blocks or, when that is 0, one residency wave of the variant, at most `cap_per_cu`
+// blocks per CU (0: no cap). Never more blocks than the batch has tiles for.
+template <auto Kernel>
+void launch_variant(const MainArgs& a, const DevProgram& prog, int grid, int auto_grid, int cap_per_cu, uint32_t dyn,
+                    hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    const uint32_t needed = (a.ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
+    int g = grid;
+    if (g <= 0) {
+        g = auto_grid > 0 ? auto_grid : resident_grid<Kernel>(dyn);
+        if (cap_per_cu) g = std::min(g, cap_per_cu * cu_count());
+    }
+    if ((uint32_t)g > needed) g = (int)(needed ? needed : 1);
+    launch(Kernel, dim3(g), dim3(kBlock), dyn, st, e0, e1, a, prog);
+}
+
 template <int FL, int REC, int F>
 void launch_t(const MainArgs& a, const DevProgram& prog, int grid, bool pf, hipStream_t st, hipEvent_t e0,
               hipEvent_t e1) {
-    const uint32_t needed = (a.ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
     const uint32_t dyn = F == 2 ? (a.dfa_bytes + 15u) & ~15u : 0u;
-    auto go = [&](auto kernel, int resident) {
-        int g = grid > 0 ? grid : resident;
-        // Fixed stride: two blocks (8 waves) per CU parse-only, three with a filter. C2
-        // measured 0.416 ms at the residency (7 blocks/CU), 0.403 at 3, 0.387 at 2, 0.56
-        // at 1 (4 processes each): fewer concurrent read and write streams suit HBM
-        // better; with the final kernels 0.338-0.341 at 2 against 0.353-0.356 at 3. With
-        // the filter (its decision / verdict stores and the slot loop per tile) the 64-B
-        // parse+filter headline needs more waves: 0.366-0.368 ms at 3 blocks/CU against
-        // 0.378-0.379 at 4 and 0.420-0.426 at 2 (round 2, alternating processes, 3
-        // passes each; round 1's code was best at 4).
-        // With the late issue (bt_parse_filter_main) the filter no longer needs the third
-        // block: c2f 0.327 ms at 2 blocks/CU against 0.343-0.350 at 3 without it.
-        if (FL >= 0 && grid <= 0) g = std::min(g, (F && !late_issue(FL, REC, F, false) ? 3 : 2) * cu_count());
-        if ((uint32_t)g > needed) g = (int)(needed ? needed : 1);
-        if (e0 || e1)
-            hipExtLaunchKernelGGL(kernel, dim3(g), dim3(kBlock), dyn, st, e0, e1, 0, a, prog);
-        else
-            hipLaunchKernelGGL(kernel, dim3(g), dim3(kBlock), dyn, st, a, prog);
-    };
     // Not for PAYLOAD programs (F == 2): bt_parse_filter_main at its residency hides the window
     // loads and the walk better than the pipe at 2 blocks/CU (C3 with /GET|POST/ first 0.885
     // against 0.98 ms, filter-only 0.60 against 0.87; tools/payload_ab.py with BT_NO_PIPE).
-    if constexpr (FL < 0 && F != 2 && (REC == kRecTiled || REC == kRecNone)) {
+    if constexpr (FL < 0 && pipe_variant(REC, F, 1) && pipe_variant(REC, F, 2)) {
         if (pf && a.desc && (a.nt & 1u) && use_pipe()) {
             // At most 2 blocks/CU (the residency is 3): with the filter slots evaluated side
             // by side, C3 0.491 against 0.498 ms and C4 0.915 against 0.948 at the residency
             // (profiles/r02/ab/pipe_grid.txt; before that change the residency was level or
             // better).
-            const int cap2 = 2 * cu_count();
-            if (a.desc_words == 1)
-                go(bt_parse_filter_pipe<REC, F, 1>,
-                   grid > 0 ? 0 : std::min(cap2, resident_grid<bt_parse_filter_pipe<REC, F, 1>>(dyn)));
-            else
-                go(bt_parse_filter_pipe<REC, F, 2>,
-                   grid > 0 ? 0 : std::min(cap2, resident_grid<bt_parse_filter_pipe<REC, F, 2>>(dyn)));
+            if (a.desc_words == 1) launch_variant<bt_parse_filter_pipe<REC, F, 1>>(a, prog, grid, 0, 2, dyn, st, e0, e1);
+            else launch_variant<bt_parse_filter_pipe<REC, F, 2>>(a, prog, grid, 0, 2, dyn, st, e0, e1);
             return;
         }
     }
-    static const bool fixed_pf = [] {   // A/B: next-tile prefetch in fixed-stride mode
-        const char* e = getenv("BT_FIXED_PREFETCH");
-        return e && *e && *e != '0';
-    }();
-    // PAYLOAD programs in descriptor mode: no next-tile prefetch (main_waves_per_eu)
-    if (FL < 0 && F == 2) pf = false;
-    // PAYLOAD programs in descriptor mode run one block per 12 tiles (three per wave), not one
-    // residency wave of blocks: without the prefetch there is nothing for a persistent block to
-    // carry from tile to tile, and a residency grid that fills every CU leaves none for the
-    // previous step's compaction, so that some of its blocks start only when others end (C3 with
-    // /GET|POST/ first, pipelined steps: 0.771-0.775 ms at one tile per wave against 1.080-1.142
-    // at the residency and 0.892-0.895 at 3 blocks/CU; two / three / four / eight / sixteen tiles
-    // per wave 0.775-0.778 / 0.753 / 0.756-0.759 / 0.764-0.767 / 0.803 ms; tools/gpu_payload_grid.sh,
-    // profiles/r06/payload/grid/).
-    // BT_PAYLOAD_GRID (A/B): blocks per CU instead, 0 = the residency, -k = one block per 4k tiles.
-    static const int pay_grid = [] {
-        const char* e = getenv("BT_PAYLOAD_GRID");
-        return e && *e ? atoi(e) : -3;
-    }();
-    if (pf && (FL < 0 || fixed_pf)) go(bt_parse_filter_main<FL, REC, F, true>, grid > 0 ? 0 : resident_grid<bt_parse_filter_main<FL, REC, F, true>>(dyn));
-    else if (FL < 0 && F == 2 && grid <= 0 && pay_grid)
-        go(bt_parse_filter_main<FL, REC, F, false>,
-           pay_grid < 0 ? (int)((needed + (uint32_t)(-pay_grid) - 1u) / (uint32_t)(-pay_grid))
-                        : std::min(pay_grid * cu_count(), resident_grid<bt_parse_filter_main<FL, REC, F, false>>(dyn)));
-    else go(bt_parse_filter_main<FL, REC, F, false>, grid > 0 ? 0 : resident_grid<bt_parse_filter_main<FL, REC, F, false>>(dyn));
+    if constexpr (main_variant(FL, REC, F, true)) {   // descriptor mode, no PAYLOAD slot
+        if (pf) {
+            launch_variant<bt_parse_filter_main<FL, REC, F, true>>(a, prog, grid, 0, 0, dyn, st, e0, e1);
+            return;
+        }
+    }
+    if constexpr (FL < 0 && F == 2) {
+        // PAYLOAD programs in descriptor mode run one block per 12 tiles (three per wave), not one
+        // residency wave of blocks: without the prefetch there is nothing for a persistent block to
+        // carry from tile to tile, and a residency grid that fills every CU leaves none for the
+        // previous step's compaction, so that some of its blocks start only when others end (C3 with
+        // /GET|POST/ first, pipelined steps: 0.771-0.775 ms at one tile per wave against 1.080-1.142
+        // at the residency and 0.892-0.895 at 3 blocks/CU; two / three / four / eight / sixteen tiles
+        // per wave 0.775-0.778 / 0.753 / 0.756-0.759 / 0.764-0.767 / 0.803 ms; tools/gpu_payload_grid.sh,
+        // profiles/r06/payload/grid/).
+        // BT_PAYLOAD_GRID (A/B): blocks per CU instead, 0 = the residency, -k = one block per 4k tiles.
+        static const int pay_grid = [] {
+            const char* e = getenv("BT_PAYLOAD_GRID");
+            return e && *e ? atoi(e) : -3;
+        }();
+        const uint32_t needed = (a.ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
+        const int per = pay_grid < 0 ? (int)((needed + (uint32_t)(-pay_grid) - 1u) / (uint32_t)(-pay_grid)) : 0;
+        launch_variant<bt_parse_filter_main<FL, REC, F, false>>(a, prog, grid, per, std::max(pay_grid, 0), dyn, st, e0, e1);
+        return;
+    }
+    // Fixed stride: two blocks (8 waves) per CU parse-only, three with a filter. C2
+    // measured 0.416 ms at the residency (7 blocks/CU), 0.403 at 3, 0.387 at 2, 0.56
+    // at 1 (4 processes each): fewer concurrent read and write streams suit HBM
+    // better; with the final kernels 0.338-0.341 at 2 against 0.353-0.356 at 3. With
+    // the filter (its decision / verdict stores and the slot loop per tile) the 64-B
+    // parse+filter headline needs more waves: 0.366-0.368 ms at 3 blocks/CU against
+    // 0.378-0.379 at 4 and 0.420-0.426 at 2 (round 2, alternating processes, 3
+    // passes each; round 1's code was best at 4).
+    // With the late issue (bt_parse_filter_main) the filter no longer needs the third
+    // block: c2f 0.327 ms at 2 blocks/CU against 0.343-0.350 at 3 without it.
+    constexpr int cap = FL < 0 ? 0 : F && !late_issue(FL, REC, F) ? 3 : 2;
+    launch_variant<bt_parse_filter_main<FL, REC, F, false>>(a, prog, grid, 0, cap, dyn, st, e0, e1);
 }
 
 template <int FL>
@@ -1334,7 +1267,7 @@ int launch_main(const MainArgs& a, const DevProgram& prog, int rec_layout, bool 
     }
     // Next-tile prefetch: the pipe kernel always prefetches (BT_OPT_NO_PREFETCH selects
     // bt_parse_filter_main without it). In bt_parse_filter_main it pays for descriptor
-    // mode (+3 % C3) but not for fixed stride (-16 % C2); launch_t drops it there.
+    // mode (+3 % C3) but not for fixed stride (-16 % C2), which has no such variant.
     // the filter variant: none, built-in slots only, or with PAYLOAD DFAs
     const int f = !filter ? 0 : a.dfa_bytes ? 2 : 1;
     switch (fl) {
@@ -1359,27 +1292,6 @@ int launch_compact(const uint64_t* verdict, uint32_t n, uint32_t* chunk_sums, ui
     return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
 }
 
-uint32_t bounds_take_main(void* stream, BoundsLog* first) {
-#ifdef BT_DEBUG_BOUNDS
-    if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return 0;
-    BoundsLog log{};
-    if (hipMemcpyFromSymbol(&log, HIP_SYMBOL(g_bounds_main), sizeof(log)) != hipSuccess) return 0;
-    if (log.count) {
-        const BoundsLog zero{};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_main), &zero, sizeof(zero));
-        if (first) *first = log;
-    }
-    return log.count;
-#else
-    (void)stream;
-    (void)first;
-    return 0;
-#endif
-}
-
-int device_grid_blocks(int device) {
-    (void)device;
-    return 0;   // auto: one residency wave per kernel variant (resident_grid)
-}
+uint32_t bounds_take_main(void* stream, BoundsLog* first) { return bounds_take(g_bounds_main, stream, first); }
 
 }  // namespace bt

@@ -22,23 +22,15 @@
 //                 byte by byte (the neighbouring tile's wave writes the other bytes).
 // Every source byte is read under `0 <= offset < bytes` (zeros otherwise); every store is to
 // a byte of a record whose whole slot ends at or below cap.
-#include <hip/hip_ext.h>
-#include <hip/hip_runtime.h>
-
+#include "bt_dev_util.h"
+#include "bt_hip_launch.h"
 #include "bt_pack.h"
 
 namespace bt {
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 u32x4_any __attribute__((aligned(1)));   // a 16-B load at any byte alignment
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -270,14 +262,8 @@ int launch_pass_pack(const PackArgs& a, void* stream, void* timing_start, void* 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipEvent_t e0 = reinterpret_cast<hipEvent_t>(timing_start), e1 = reinterpret_cast<hipEvent_t>(timing_stop);
     uint32_t* tile_sums = reinterpret_cast<uint32_t*>(a.sums + a.nchunks);
-    if (e0 || e1) {
-        hipExtLaunchKernelGGL(bt_pack_sums, dim3(a.nchunks), dim3(256), 0, st, e0, nullptr, 0, a, tile_sums);
-        hipExtLaunchKernelGGL(bt_pack_copy, dim3(a.nchunks), dim3(256), 0, st, nullptr, e1, 0, a,
-                              (const uint32_t*)tile_sums);
-    } else {
-        hipLaunchKernelGGL(bt_pack_sums, dim3(a.nchunks), dim3(256), 0, st, a, tile_sums);
-        hipLaunchKernelGGL(bt_pack_copy, dim3(a.nchunks), dim3(256), 0, st, a, (const uint32_t*)tile_sums);
-    }
+    launch(bt_pack_sums, dim3(a.nchunks), dim3(256), 0, st, e0, nullptr, a, tile_sums);
+    launch(bt_pack_copy, dim3(a.nchunks), dim3(256), 0, st, nullptr, e1, a, (const uint32_t*)tile_sums);
     return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
 }
 

@@ -27,13 +27,11 @@
 //                walks (bt_payload_walk.h) over the staged row, the others eval_slot.
 // bt_verdict_words rebuilds the verdict words from the final decision bytes (the resume kernel
 // writes none: a word holds frames of other lanes' tiles, and no atomics touch mapped memory).
-#include <hip/hip_ext.h>
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <mutex>
 
+#include "bt_dev_util.h"
 #include "bt_device.h"
+#include "bt_hip_launch.h"
 #include "bt_payload_walk.h"
 #include "bt_slot_eval.h"
 
@@ -45,13 +43,6 @@ __device__ BoundsLog g_bounds_resume;
 namespace {
 
 constexpr uint32_t kQueue = 128;   // a wave's pending work items: < 64 left over + one tile's 64
-
-__device__ __forceinline__ void wave_sync_lds() {
-    // lanes of one wavefront hand rows and queue entries to each other through LDS
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ uint4 ld16_in(const ResumeArgs& a, uint64_t addr, bool ok) {
     // a chunk that would pass the read limit reads as zeros, as in the main kernel
@@ -97,20 +88,11 @@ __device__ __forceinline__ void resume_items(const ResumeArgs& a, const DevProgr
             dst[0] = v[j].x; dst[1] = v[j].y; dst[2] = v[j].z; dst[3] = v[j].w;
         }
     }
-    wave_sync_lds();
+    wave_lds_sync();
 
     // the frame's first 40 bytes from the row (bytes 12..37 and 14 are what is read of them)
     uint32_t w0[10];
-    {
-        const uint32_t d = s >> 2, sh = s & 3u;
-        uint32_t prev = row[d];
-#pragma unroll
-        for (int k = 0; k < 10; ++k) {
-            const uint32_t next = row[d + k + 1];
-            w0[k] = __builtin_amdgcn_alignbyte(next, prev, sh);
-            prev = next;
-        }
-    }
+    window<10>(row, s, w0);
     const FilterIn x = filter_in([&w0](uint32_t i) { return byte_of(w0, (int)i); }, len);
     uint32_t po;
     const uint32_t L = payload_window(len, w0, po);
@@ -129,7 +111,7 @@ __device__ __forceinline__ void resume_items(const ResumeArgs& a, const DevProgr
         const uint32_t t0 = src[0], t1 = src[1], t2 = src[2], t3 = src[3];
         dst[0] = t0; dst[1] = t1; dst[2] = t2; dst[3] = t3;
     }
-    wave_sync_lds();
+    wave_lds_sync();
     {
         const uint32_t al_lo = (uint32_t)al, al_hi = (uint32_t)(al >> 32), nk = nch | (kept << 8);
         const uint32_t k = lane & 7u;
@@ -154,7 +136,7 @@ __device__ __forceinline__ void resume_items(const ResumeArgs& a, const DevProgr
                 }
         }
     }
-    wave_sync_lds();
+    wave_lds_sync();
 
     // ---- CHAIN: slots slot0 .. n-1 as filter_packet<2> evaluates them over whole frames ----
     uint32_t code = BT_DECIDE_PASS, slot = prog.n ? prog.n - 1u : 0u;
@@ -184,7 +166,7 @@ __device__ __forceinline__ void resume_items(const ResumeArgs& a, const DevProgr
         }
     }
     if (have && BT_IN(&g_bounds_resume, kSiteDecide, idx, a.n)) a.decide[idx] = (uint8_t)((code << 6) | slot);
-    wave_sync_lds();   // the next batch overwrites this wave's rows
+    wave_lds_sync();   // the next batch overwrites this wave's rows
 }
 
 __global__ __launch_bounds__(kBlock) void bt_payload_resume(ResumeArgs a, DevProgram prog) {
@@ -194,12 +176,7 @@ __global__ __launch_bounds__(kBlock) void bt_payload_resume(ResumeArgs a, DevPro
     const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform
     uint32_t* img = lds_all + wid * (kWave * kRowDwords + kQueue);
     uint32_t* queue = img + kWave * kRowDwords;
-    {   // uniform: the whole block copies the pool once
-        const uint4* src = reinterpret_cast<const uint4*>(a.dfa);
-        for (uint32_t k = threadIdx.x; k < (a.dfa_bytes + 15u) / 16u && BT_IN(&g_bounds_resume, kSitePayload, 16u * k, kDfaPoolMax); k += kBlock)
-            dyn_lds[k] = src[k];
-        __syncthreads();
-    }
+    copy_dfa_pool(dyn_lds, a.dfa, a.dfa_bytes, &g_bounds_resume);
     const uint8_t* dfa_lds = reinterpret_cast<const uint8_t*>(dyn_lds);
 
     // the program's PAYLOAD slots as a mask (BT_MAX_FILTERS = 64 slots)
@@ -224,18 +201,18 @@ __global__ __launch_bounds__(kBlock) void bt_payload_resume(ResumeArgs a, DevPro
         if (work) queue[qn + (uint32_t)__popcll(m & below)] = t * 64u + lane;   // qn < 64: inside kQueue
         qn += (uint32_t)__popcll(m);
         if (qn >= 64u) {
-            wave_sync_lds();
+            wave_lds_sync();
             const uint32_t idx = queue[lane];
             const uint32_t rest = qn - 64u;   // < 64
             const uint32_t tail = lane < rest ? queue[64u + lane] : 0u;
-            wave_sync_lds();
+            wave_lds_sync();
             if (lane < rest) queue[lane] = tail;
             qn = rest;
             resume_items(a, prog, dfa_lds, img, lane, idx, true);
         }
     }
     if (qn) {   // the wave's last, partial batch
-        wave_sync_lds();
+        wave_lds_sync();
         const bool have = lane < qn;
         const uint32_t idx = have ? queue[lane] : 0u;
         resume_items(a, prog, dfa_lds, img, lane, idx, have);
@@ -254,25 +231,6 @@ __global__ __launch_bounds__(kBlock) void bt_verdict_words(const uint8_t* decide
     if (lane == 0 && BT_IN(&g_bounds_resume, kSiteVerdict, t, ntiles)) verdict[t] = word;
 }
 
-// Blocks per CU by the occupancy query, per dynamic-LDS size (the program's pool).
-int resume_resident(uint32_t dyn) {
-    static std::mutex mu;
-    static uint32_t last_dyn = ~0u;
-    static int last_blocks = 0;
-    std::lock_guard<std::mutex> lk(mu);
-    if (dyn != last_dyn) {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bt_payload_resume, kBlock, dyn) != hipSuccess ||
-            per_cu < 1)
-            last_blocks = 1024;
-        else
-            last_blocks = prop.multiProcessorCount * per_cu;
-        last_dyn = dyn;
-    }
-    return last_blocks;
-}
 
 }  // namespace
 
@@ -287,11 +245,8 @@ int launch_payload_resume(const ResumeArgs& a, const DevProgram& prog, void* str
     // blocks (the scan loop is persistent).
     constexpr uint32_t kScanTiles = 8;
     const uint32_t needed = (a.ntiles + kWavesPerBlock * kScanTiles - 1u) / (kWavesPerBlock * kScanTiles);
-    const int g = (int)std::max(1u, std::min(needed, (uint32_t)resume_resident(dyn)));
-    if (e0 || e1)
-        hipExtLaunchKernelGGL(bt_payload_resume, dim3(g), dim3(kBlock), dyn, st, e0, e1, 0, a, prog);
-    else
-        hipLaunchKernelGGL(bt_payload_resume, dim3(g), dim3(kBlock), dyn, st, a, prog);
+    const int g = (int)std::max(1u, std::min(needed, (uint32_t)resident_grid<bt_payload_resume>(dyn)));
+    launch(bt_payload_resume, dim3(g), dim3(kBlock), dyn, st, e0, e1, a, prog);
     return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
 }
 
@@ -303,22 +258,6 @@ int launch_verdict_words(const uint8_t* decide, uint32_t n, uint64_t* verdict, v
     return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
 }
 
-uint32_t bounds_take_resume(void* stream, BoundsLog* first) {
-#ifdef BT_DEBUG_BOUNDS
-    if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return 0;
-    BoundsLog log{};
-    if (hipMemcpyFromSymbol(&log, HIP_SYMBOL(g_bounds_resume), sizeof(log)) != hipSuccess) return 0;
-    if (log.count) {
-        const BoundsLog zero{};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_resume), &zero, sizeof(zero));
-        if (first) *first = log;
-    }
-    return log.count;
-#else
-    (void)stream;
-    (void)first;
-    return 0;
-#endif
-}
+uint32_t bounds_take_resume(void* stream, BoundsLog* first) { return bounds_take(g_bounds_resume, stream, first); }
 
 }  // namespace bt

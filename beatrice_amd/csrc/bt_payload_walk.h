@@ -9,17 +9,11 @@
 
 #include <type_traits>
 
+#include "bt_dev_util.h"
 #include "bt_device.h"
 
 namespace bt {
 namespace {
-
-__device__ __forceinline__ uint32_t byte_of(const uint32_t* w, int i) {
-    return (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-}
-__device__ __forceinline__ uint32_t be16_of(const uint32_t* w, int i) {
-    return (byte_of(w, i) << 8) | byte_of(w, i + 1);
-}
 
 // applyPayloadFilter's window of a frame (eval_payload's gates): its start offset in the
 // frame (po) and length L; L = 0 when the filter returns false without a search.

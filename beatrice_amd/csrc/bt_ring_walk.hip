@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bt_device.h"
+#include "bt_hip_launch.h"
 
 namespace bt {
 
@@ -74,22 +75,6 @@ int launch_ring_walk(const RingWalkArgs& a, void* stream) {
     return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
 }
 
-uint32_t bounds_take_ring(void* stream, BoundsLog* first) {
-#ifdef BT_DEBUG_BOUNDS
-    if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return 0;
-    BoundsLog log{};
-    if (hipMemcpyFromSymbol(&log, HIP_SYMBOL(g_bounds_ring), sizeof(log)) != hipSuccess) return 0;
-    if (log.count) {
-        const BoundsLog zero{};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_ring), &zero, sizeof(zero));
-        if (first) *first = log;
-    }
-    return log.count;
-#else
-    (void)stream;
-    (void)first;
-    return 0;
-#endif
-}
+uint32_t bounds_take_ring(void* stream, BoundsLog* first) { return bounds_take(g_bounds_ring, stream, first); }
 
 }  // namespace bt

@@ -380,6 +380,69 @@ def test_kernel_forms_agree(form):
         ctx.close()
 
 
+def test_blocked_tile_ranges():
+    """Blocked tile order over 8 waves in the two kernels KERNEL_FORMS does not run it in: the
+    late-issue bt_parse_filter_main (64-B fixed stride) and bt_parse_filter_pipe with xdp_desc
+    descriptors. 1,541 packets are 25 tiles: ranges of 4 tiles, one wave with a single tile and one
+    with none (t_end = min(ntiles, t + per), the pipe's empty-range return). The fixed-stride form
+    also with only the decisions, only the verdict words and only the pass list requested: the
+    empty buffer ranges of the counted decision / verdict stores."""
+    for form in ("fixed64_late_issue", "xdp_pipe"):
+        _blocked_tile_ranges(form)
+
+
+def _blocked_tile_ranges(form):
+    n_all = 1541
+    filters = [{"type": abi.PROTOCOL, "expr": "udp", "priority": 3},
+               {"type": abi.IP_RANGE, "expr": "10.0.0.0/8", "priority": 2},
+               {"type": abi.PORT_RANGE, "expr": "1000-2000", "priority": 1}]
+    fixed = form == "fixed64_late_issue"
+    data, desc = synth.capture(synth.C2 if fixed else synth.FUZZ, n_all, seed=0xB10C)
+
+    def run(ctx, n, **outs):
+        if fixed:
+            return run_one(abi.DeviceRun(ctx, np.ascontiguousarray(data[:n * 64]), None, n, stride=64, **outs))
+        xdp = np.zeros((n, 2), np.uint64)   # struct xdp_desc {u64 addr; u32 len; u32 options}
+        xdp[:, 0] = synth.desc_off(desc[:n]).astype(np.uint64)
+        xdp[:, 1] = synth.desc_len(desc[:n]).astype(np.uint64)
+        r = abi.DeviceRun(ctx, data, xdp.reshape(-1), n, **outs)
+        r.batch = abi.Batch(r.d_data.ptr, r.d_desc.ptr, 0, n, data.nbytes, abi.DESC_XDP, 0)
+        return run_one(r)
+
+    def run_one(r):
+        r.run()
+        out = r.fetch()
+        r.free()
+        return out
+
+    ctx = abi.Context(0, flags=abi.OPT_TILE_BLOCKED, grid_waves=8)
+    try:
+        ctx.compile(filters)
+        for n in (1, 63, 65, n_all):
+            if fixed:
+                rec, dec, npass = ol.oracle_run(np.ascontiguousarray(data[:n * 64]), None, n, filters, stride=64)
+            else:
+                rec, dec, npass = ol.oracle_run(data, np.ascontiguousarray(desc[:n]), n, filters)
+            passing = np.nonzero((dec >> 6) == 0)[0].astype(np.uint32)
+            out = run(ctx, n)
+            assert np.array_equal(out["records"], rec), f"{form} n={n}: records"
+            assert np.array_equal(out["decide"], dec), f"{form} n={n}: decisions"
+            assert out["n_pass"] == npass
+            check_filter_outputs(out, n)
+            if not fixed:
+                continue
+            out = run(ctx, n, records=False, verdict=False, pass_idx=False)
+            assert np.array_equal(out["decide"], dec), f"{form} n={n}: decisions alone"
+            out = run(ctx, n, records=False, decide=False, pass_idx=False)
+            bits = np.unpackbits(out["verdict"].view(np.uint8), bitorder="little")
+            assert np.array_equal(np.nonzero(bits)[0], passing), f"{form} n={n}: verdict words alone"
+            out = run(ctx, n, records=False, decide=False, verdict=False)
+            assert out["n_pass"] == npass, f"{form} n={n}: pass list alone"
+            assert np.array_equal(out["pass_idx"], passing), f"{form} n={n}: pass list alone"
+    finally:
+        ctx.close()
+
+
 FAR = 3 << 29   # 1.5 GiB
 
 

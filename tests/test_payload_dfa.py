@@ -2,7 +2,7 @@
 SURVEY §8(f) 3), checked without a GPU:
 
   * against std::regex_search itself — the libstdc++ function the reference's
-    applyPayloadFilter calls — by the differential fuzzer tests/cpp/test_regex_dfa
+    applyPayloadFilter calls — by the differential fuzzer tests/cpp/test_regex_dfa.cpp
     (random patterns over the modelled ECMAScript subset x random byte strings, plus
     the applyPayloadFilter window on synthetic frames);
   * against the compiled reference's PacketFilter outcomes in the goldens: every
@@ -15,13 +15,14 @@ import numpy as np
 import pytest
 
 from beatrice_amd import abi, synth
-from conftest import GOLDEN, load_golden
+from conftest import load_golden
 
-FUZZ_BIN = os.path.join(os.path.dirname(GOLDEN), "cpp", "test_regex_dfa")
+# built beside the library (make -C tests/cpp), not under tests/
+FUZZ_BIN = os.path.join(os.path.dirname(os.path.abspath(abi.__file__)), "test_regex_dfa")
 
 
 def test_dfa_fuzz_against_std_regex():
-    assert os.path.exists(FUZZ_BIN), "tests/cpp/test_regex_dfa not built (make -C tests/cpp)"
+    assert os.path.exists(FUZZ_BIN), "beatrice_amd/test_regex_dfa not built (make -C tests/cpp)"
     r = subprocess.run([FUZZ_BIN, "200", "60", "4242"], capture_output=True, text=True, timeout=600)
     print(r.stdout[-2000:])
     assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-3000:]
