@@ -114,6 +114,35 @@ class PackOut(ctypes.Structure):
                 ("total", ctypes.c_void_p), ("n_packed", ctypes.c_void_p)]
 
 
+TALLY_STOP_AT_THROW = 0x1   # count only the packets before the first DECIDE_THROW
+TALLY_ACCUMULATE = 0x2      # add to the counts *out already holds
+LAYER_NAMES = ("ethernet", "vlan0", "vlan1", "ipv4", "ipv6", "tcp", "udp", "icmp")   # bit k of present / ok
+
+
+class Tally(ctypes.Structure):
+    """bt_tally (2,304 B): bt_tally_device's counts of a device-resident batch."""
+    _fields_ = [("n", ctypes.c_uint64), ("scanned", ctypes.c_uint64), ("first_throw", ctypes.c_uint64),
+                ("first_host", ctypes.c_uint64), ("first_throw_slot", ctypes.c_uint32),
+                ("first_host_slot", ctypes.c_uint32), ("code", ctypes.c_uint64 * 4),
+                ("slot", (ctypes.c_uint64 * 64) * 4), ("bytes", ctypes.c_uint64 * 4),
+                ("layer_present", ctypes.c_uint64 * 8), ("layer_ok", ctypes.c_uint64 * 8),
+                ("reserved", ctypes.c_uint64 * 3)]
+
+    def as_dict(self) -> dict:
+        """Plain ints and lists; slot[code][s]."""
+        out = {k: int(getattr(self, k)) for k in ("n", "scanned", "first_throw", "first_host", "first_throw_slot",
+                                                  "first_host_slot")}
+        for k in ("code", "bytes", "layer_present", "layer_ok", "reserved"):
+            out[k] = [int(x) for x in getattr(self, k)]
+        out["slot"] = [[int(x) for x in row] for row in self.slot]
+        return out
+
+    @classmethod
+    def from_bytes(cls, buf) -> "Tally":
+        """The struct held in 2,304 downloaded bytes."""
+        return cls.from_buffer_copy(bytes(bytearray(_byte_view(buf)[:ctypes.sizeof(cls)])))
+
+
 class PcapInfo(ctypes.Structure):
     """bt_pcap_info: what bt_pcap_index read from a capture file's global header."""
     _fields_ = [("magic", ctypes.c_uint32), ("swapped", ctypes.c_uint32), ("nanosecond", ctypes.c_uint32),
@@ -222,7 +251,7 @@ EXPORTS = [
     "bt_group_host_unregister", "bt_group_parse_filter_mapped", "bt_context_placement", "bt_node_cpus",
     "bt_usable_cpus", "bt_extract_host", "bt_filter_dfa_pool", "bt_group_split_plan",
     "bt_group_host_parallel", "bt_pass_pack_device", "bt_pcap_index", "bt_pcap_filter", "bt_time_pass_pack",
-    "bt_time_copy_d2d",
+    "bt_time_copy_d2d", "bt_tally_device", "bt_time_tally", "bt_time_tally_host",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -258,6 +287,9 @@ def lib() -> ctypes.CDLL:
         "bt_time_pass_pack": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(PackOpts),
                                              ctypes.POINTER(PackOut), u32, vp]),
         "bt_time_copy_d2d": (ctypes.c_int, [vp, vp, vp, u64, u32, vp]),
+        "bt_tally_device": (ctypes.c_int, [vp, vp, u32, ctypes.POINTER(Batch), vp, u32, u32, vp, vp]),
+        "bt_time_tally": (ctypes.c_int, [vp, vp, u32, ctypes.POINTER(Batch), vp, u32, u32, vp, u32, vp]),
+        "bt_time_tally_host": (ctypes.c_int, [vp, vp, u32, u32, vp, vp, vp]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -590,6 +622,18 @@ class Context:
         out = PackOut(ptr(out_bytes), cap, ptr(desc), ptr(total), ptr(n_packed))
         _check(lib().bt_pass_pack_device(self.h, ctypes.byref(batch), ptr(select_dev), ctypes.byref(po),
                                          ctypes.byref(out), stream))
+
+    def tally_device(self, decide_ptr, n: int, out_ptr, frames: "Batch | None" = None, records_ptr=None,
+                     n_cap: int = 0, flags: int = 0, stream=None):
+        """bt_tally_device: the counts of a device-resident batch into the bt_tally (Tally, 2,304 B
+        of device-visible memory, 8-byte aligned) at out_ptr. decide_ptr: the n decision bytes of
+        a filter call (any alignment; None for the layer counts alone); frames: the batch, for the
+        byte sums (only lengths are read); records_ptr / n_cap: the call's records in the context's
+        layout, for the layer counts. flags: TALLY_STOP_AT_THROW, TALLY_ACCUMULATE. Pointers are
+        addresses or DeviceBuffers. Asynchronous on `stream`."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        _check(lib().bt_tally_device(self.h, ptr(decide_ptr), n, ctypes.byref(frames) if frames is not None else None,
+                                     ptr(records_ptr), n_cap, flags, ptr(out_ptr), stream))
 
     def pcap_filter(self, buf):
         """bt_pcap_filter: the classic pcap file in `buf` through the compiled program. Returns

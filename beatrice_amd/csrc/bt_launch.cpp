@@ -19,7 +19,9 @@ void free_ws(bt_ctx* c) {
         if (w.chunk_sums) (void)hipFree(w.chunk_sums);
         if (w.verdict) (void)hipFree(w.verdict);
         if (w.pack_sums) (void)hipFree(w.pack_sums);
+        if (w.tally_parts) (void)hipFree(w.tally_parts);
         w.pack_sums = nullptr;
+        w.tally_parts = nullptr;
         w.chunk_sums = nullptr; w.verdict = nullptr; w.last = nullptr; w.lazy = false;
     }
     c->ws.cap = 0;
@@ -45,6 +47,7 @@ int ensure_ws(bt_ctx* c, uint32_t n) {
         HIP_TRY(hipMalloc(&w.chunk_sums, (size_t)nchunks * 4));
         HIP_TRY(hipMalloc(&w.verdict, (size_t)ntiles * 8));
         HIP_TRY(hipMalloc(&w.pack_sums, (size_t)nchunks * sizeof(PackChunkSum) + (size_t)ntiles * 4));
+        HIP_TRY(hipMalloc(&w.tally_parts, (size_t)nchunks * sizeof(TallyPartial)));
     }
     for (auto& e : c->ws.main_done)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <vector>
 
 #include "bt_ctx.h"
 #include "bt_hip_util.h"
@@ -97,6 +98,79 @@ int bt_time_pass_pack(bt_ctx* c, const bt_batch* b, const uint64_t* select, cons
         }
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
+int bt_time_tally(bt_ctx* c, const uint8_t* decide, uint32_t n, const bt_batch* frames, const void* records,
+                  uint32_t n_cap, uint32_t flags, bt_tally* out, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !n || !iters || !ms) return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int rc = run_tally(c, decide, n, frames, records, n_cap, flags, out, c->stream, c->timing.tev[2 * i],
+                               c->timing.tev[2 * i + 1])) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
+// What the tally replaces: the decision bytes copied to pinned host memory, then the 16-part host
+// scan of GpuPacketFilter::scanParallel's inner loop (counted, passed, rejected per slot, up to
+// the first throw of each part) on the context's host threads.
+int bt_time_tally_host(bt_ctx* c, const uint8_t* decide, uint32_t n, uint32_t iters, float* copy_ms, float* scan_ms,
+                       uint64_t* counts) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !decide || !n || !iters || !copy_ms || !scan_ms) return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    uint8_t* h = nullptr;
+    HIP_TRY(hipHostMalloc(&h, n, hipHostMallocDefault));
+    std::memset(h, 0, n);   // first touch outside the timed part
+    constexpr uint32_t kParts = 16;
+    struct Part { uint64_t counted = 0, passed = 0, rejected[64] = {}; bool stopped = false; char pad[64]; };
+    HostPool& pool = pool_of(c);   // the threads bt_host_parallel lends to scanParallel
+    const unsigned T = pool.size();
+    const auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto ms = [](auto a, auto b) { return std::chrono::duration<float, std::milli>(b - a).count(); };
+    hipError_t err = hipSuccess;
+    std::vector<Part> parts(kParts);
+    for (uint32_t it = 0; it < iters && err == hipSuccess; ++it) {
+        const auto t0 = now();
+        err = hipMemcpyAsync(h, decide, n, hipMemcpyDeviceToHost, c->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+        const auto t1 = now();
+        parts.assign(kParts, Part{});
+        pool.run([&](unsigned w) {
+                for (uint32_t k = w; k < kParts; k += T) {
+                    Part& p = parts[k];
+                    const size_t lo = (size_t)n * k / kParts, hi = (size_t)n * (k + 1) / kParts;
+                    for (size_t i = lo; i < hi; ++i) {
+                        const uint32_t d = h[i], code = d >> 6;
+                        if (code >= BT_DECIDE_THROW) { p.stopped = true; break; }
+                        ++p.counted;
+                        if (code == BT_DECIDE_PASS) ++p.passed;
+                        else ++p.rejected[d & 63u];
+                    }
+                }
+            });
+        copy_ms[it] = ms(t0, t1);
+        scan_ms[it] = ms(t1, now());
+    }
+    if (counts) {   // counted, passed: so that the scan's result is used (and can be checked)
+        counts[0] = counts[1] = 0;
+        for (const Part& p : parts) {
+            counts[0] += p.counted;
+            counts[1] += p.passed;
+            if (p.stopped) break;
+        }
+    }
+    (void)hipHostFree(h);
+    if (err != hipSuccess) return set_error(BT_E_INTERNAL, "bt_time_tally_host: %s", hipGetErrorString(err));
     return BT_OK;
 }
 

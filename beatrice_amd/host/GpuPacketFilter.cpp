@@ -2,6 +2,7 @@
 // src/PacketFilter.cpp:<line> (Open-Sentra/beatrice).
 #include "GpuPacketFilter.hpp"
 
+#include "beatrice_gpu_bench.h"   // bt_stream_synchronize: the wait on a caller's stream
 #include "bt_slot_eval.h"
 
 #include <algorithm>
@@ -98,7 +99,13 @@ void GpuPacketFilter::open(const std::vector<int>& devices, const bt_opts* opts)
     ctx_ = bt_group_member(group_, 0);
 }
 
-GpuPacketFilter::~GpuPacketFilter() { bt_group_destroy(group_); }
+GpuPacketFilter::~GpuPacketFilter() {
+    if (tallyHost_) {
+        (void)bt_host_unregister(ctx_, tallyHost_);
+        std::free(tallyHost_);
+    }
+    bt_group_destroy(group_);
+}
 
 Result<void> GpuPacketFilter::addFilter(const std::string& name, const FilterConfig& config) {
     std::unique_lock<std::shared_mutex> lock(filtersMutex_);   // :19-31
@@ -732,6 +739,59 @@ std::vector<uint32_t> GpuPacketFilter::classifyMapped(const bt_batch& batch, con
     t.rethrowIfAny(*this, out.decide);
     setTiming(device_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count());
     return pass;
+}
+
+GpuPacketFilter::DeviceCounts GpuPacketFilter::classifyDevice(const bt_batch& batch, const bt_outputs& out,
+                                                             void* stream) {
+    DeviceCounts dc;
+    const auto lock = lockProgram();
+    const InFlight busy(inFlight_);
+    if (!out.decide) throw std::invalid_argument("GpuPacketFilter::classifyDevice: decide required");
+    for (const Slot& s : program_)
+        if (s.compiled.kind == BT_K_HOST)
+            throw std::invalid_argument("GpuPacketFilter::classifyDevice: filter '" + s.name +
+                                        "' is decided on the host (a CUSTOM callback or a PAYLOAD regex outside the "
+                                        "GPU subset): the device alone cannot decide its packets");
+    if (!batch.n) return dc;
+    std::lock_guard<std::mutex> one(tallyMutex_);
+    if (!tallyHost_) {
+        constexpr size_t kPage = 4096;
+        static_assert(sizeof(bt_tally) <= kPage, "the tally fits one page");
+        void* p = std::aligned_alloc(kPage, kPage);
+        if (!p) throw std::bad_alloc();
+        if (bt_host_register(ctx_, p, kPage, &tallyDev_) != BT_OK) {
+            std::free(p);
+            throw std::runtime_error(std::string("GpuPacketFilter::classifyDevice: ") + bt_last_error());
+        }
+        tallyHost_ = static_cast<bt_tally*>(p);
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (bt_parse_filter_device(ctx_, &batch, &out, stream) != BT_OK ||
+        bt_tally_device(ctx_, out.decide, batch.n, &batch, out.records, out.n_cap, BT_TALLY_STOP_AT_THROW,
+                        static_cast<bt_tally*>(tallyDev_), stream) != BT_OK) {
+        const std::string why = bt_last_error();
+        (void)(stream ? bt_stream_synchronize(ctx_, stream) : bt_synchronize(ctx_));
+        throw std::runtime_error("GpuPacketFilter::classifyDevice: " + why);
+    }
+    if ((stream ? bt_stream_synchronize(ctx_, stream) : bt_synchronize(ctx_)) != BT_OK)
+        throw std::runtime_error(std::string("GpuPacketFilter::classifyDevice: ") + bt_last_error());
+    const auto t1 = std::chrono::steady_clock::now();
+    dc.tally = *tallyHost_;
+    const bt_tally& y = dc.tally;
+    // the tally as the host scan would have left it: the packets before the first throw
+    Tally t;
+    t.counted = dc.counted = y.scanned;
+    t.passed = dc.passed = y.code[BT_DECIDE_PASS];
+    t.rejected.assign(program_.size() + 1, 0);
+    for (size_t s = 0; s < program_.size(); ++s) t.rejected[s] = y.slot[BT_DECIDE_REJECT][s];
+    t.stop = (size_t)y.scanned;
+    t.threw = y.first_throw < y.n;
+    const auto per = std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0) / (int64_t)batch.n;
+    flushTally(t, per);
+    setTiming(std::chrono::duration<double>(t1 - t0).count(),
+              std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count());
+    if (t.threw) rethrow(program_.at(y.first_throw_slot));   // earlier packets are counted
+    return dc;
 }
 
 void GpuPacketFilter::registerHost(void* p, size_t bytes) {

@@ -110,6 +110,22 @@ public:
     // classify. Returns the pass indices, ascending.
     std::vector<uint32_t> classifyMapped(const bt_batch& batch, const bt_outputs& out,
                                          const std::function<Packet(uint32_t)>& packetOf);
+    // The statistics of a batch that stays on the device: `batch` and `out` hold DEVICE addresses
+    // on context()'s device (out.decide required; out.records, out.verdict, out.pass_idx / n_pass
+    // as the caller wants them). bt_parse_filter_device, then bt_tally_device with
+    // BT_TALLY_STOP_AT_THROW into a small pinned buffer the filter owns, both on `stream`
+    // (nullptr: the context's), then a wait: no per-packet output crosses PCIe, only the 2,304
+    // bytes of the tally. getStats() is updated as classify leaves it (the packets before the
+    // first throw), lastBatchTiming is set, and a throwing packet rethrows its filter's exception
+    // after that, as classify does. A program with a host-only slot (an installed CUSTOM
+    // callback, a PAYLOAD regex outside the GPU subset) is refused with std::invalid_argument
+    // before any work: the device alone cannot decide those packets.
+    struct DeviceCounts {
+        uint64_t counted = 0, passed = 0;   // what was added to packetsProcessed / packetsPassed
+        bt_tally tally{};
+    };
+    DeviceCounts classifyDevice(const bt_batch& batch, const bt_outputs& out, void* stream = nullptr);
+
     // Page-locks a host range and maps it into every device of the filter
     // (bt_group_host_register); throws std::runtime_error. unregisterHost waits for the devices.
     void registerHost(void* p, size_t bytes);
@@ -212,6 +228,11 @@ private:
     std::vector<uint8_t> dfaPool_;            // the program's PAYLOAD DFAs (bt_filter_dfa_pool)
     std::atomic<size_t> hostBelow_{kHostBelowDefault};
     BatchTiming timing_;
+    // classifyDevice's tally: one page of host memory registered with ctx_ (tallyDev_ = the
+    // device's alias of it), allocated by the first call; one call at a time writes it
+    std::mutex tallyMutex_;
+    bt_tally* tallyHost_ = nullptr;
+    void* tallyDev_ = nullptr;
 };
 
 }  // namespace gpu

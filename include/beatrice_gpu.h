@@ -81,7 +81,7 @@ extern "C" {
  * built against an older header should check bt_abi_version() >= the version they need.
  * Added within 2 (new entry points only, nothing existing changed; a host that needs them can
  * look the symbols up): bt_filter_resume_device, bt_ring_stage_tpv3_ex, bt_pass_pack_device,
- * bt_pcap_index, bt_pcap_filter. */
+ * bt_pcap_index, bt_pcap_filter, bt_tally_device. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -461,6 +461,56 @@ typedef struct bt_pack_out {           /* device-visible memory                 
 int  bt_pass_pack_device(bt_ctx* ctx, const bt_batch* frames, const uint64_t* select,
                          const bt_pack_opts* opts, const bt_pack_out* out, void* stream);
 
+/* ---- counts of a batch that stays on the device -------------------------------------
+ * What PacketFilter::getStats() (reference src/PacketFilter.cpp:374-386) and
+ * ProtocolParser::getStats() (src/parser/ProtocolParser.cpp:174-182) answer, for a batch whose
+ * per-packet outputs never cross PCIe: the decision bytes of a filter call counted by code and
+ * by deciding slot, the frame lengths summed by code, and the parsed layers counted from the
+ * records' present / ok bits. Only these 2,304 bytes go to the host.
+ *   decide   the n decision bytes of a filter call (out->decide), device-visible, any
+ *            alignment; NULL when only the layer counts are wanted.
+ *   frames   optional: the batch the decisions belong to (frames->n == n). Only lengths are
+ *            read, never frame bytes: both descriptor formats, and fixed stride with length
+ *            min(stride, 65535) as in the pack. Without `decide` it is not read at all.
+ *   records  optional: the records of the same call in the context's own layout (tiled, or
+ *            BT_OPT_RECORDS_PLANES with plane stride n_cap, or BT_OPT_RECORDS_AOS); only the
+ *            present | ok << 8 dword of packets [0, n) is read.
+ * Without BT_TALLY_ACCUMULATE every byte of *out is written (sums whose input is NULL are 0).
+ * With it n, scanned, code, slot, bytes and layer_* are added to what *out holds (a stream of
+ * batches into one tally, read once per reporting interval); the four first_* fields always
+ * describe this call alone. BT_DECIDE_HOST never stops the count. With BT_TALLY_STOP_AT_THROW,
+ * scanned == first_throw and code[BT_DECIDE_THROW] == 0; the layer counts always cover [0, n).
+ * All counts are exact. Asynchronous on `stream` (NULL = the context's stream), no host
+ * synchronisation, two kernel launches (none for n == 0, which still writes *out on the
+ * stream), no allocation once bt_reserve(n) has been called; usable right behind
+ * bt_parse_filter_device on the same stream. The kernels read nothing outside the 16-byte
+ * granules that hold decide[0 .. n), no descriptor at or past n and no record tile at or past
+ * ceil(n / 64). BT_E_INVALID_ARGUMENT: a null context or out (or an out that is not 8-byte
+ * aligned), decide and records both NULL, frames->n != n or a batch bt_parse_filter_device
+ * refuses, records with n_cap < n, unknown flag bits. */
+#define BT_TALLY_STOP_AT_THROW 0x1u  /* count only the packets before the first BT_DECIDE_THROW,
+                                        as applyFilters(vector) / classify leave the stats      */
+#define BT_TALLY_ACCUMULATE    0x2u  /* add to the counts already in *out (a stream of batches)  */
+
+typedef struct bt_tally {            /* 2,304 B, device-visible memory, 8-byte aligned           */
+    uint64_t n;                      /* packets of the batch(es)                                 */
+    uint64_t scanned;                /* packets counted below: n, or the first throw's index     */
+    uint64_t first_throw;            /* index of the first THROW decision in [0, n); n = none    */
+    uint64_t first_host;             /* index of the first HOST decision in [0, n); n = none     */
+    uint32_t first_throw_slot, first_host_slot;   /* their slots (0 when none)                   */
+    uint64_t code[4];                /* decisions of [0, scanned) by BT_DECIDE_* code            */
+    uint64_t slot[4][64];            /* ... by code and deciding slot                            */
+    uint64_t bytes[4];               /* frame lengths of [0, scanned) summed by code             */
+    uint64_t layer_present[8];       /* over [0, n): packets with bit k of bt_rec.present        */
+    uint64_t layer_ok[8];            /* ... with bit k of bt_rec.ok                              */
+    uint64_t reserved[3];            /* written as 0                                             */
+} bt_tally;
+
+int  bt_tally_device(bt_ctx* ctx, const uint8_t* decide, uint32_t n,
+                     const bt_batch* frames,     /* optional: only lengths are read -> bytes[]     */
+                     const void* records, uint32_t n_cap,   /* optional -> layer_*[]               */
+                     uint32_t flags, bt_tally* out, void* stream);
+
 /* ---- pcap capture files ------------------------------------------------------------
  * Classic pcap (24-B global header, 16-B record headers), link type 1 (Ethernet), in all four
  * magics: microsecond (0xa1b2c3d4) or nanosecond (0xa1b23c4d) timestamps, in the reader's
@@ -830,6 +880,7 @@ static_assert(sizeof(bt_rec) == BT_REC_BYTES, "bt_rec must be 96 bytes");
 static_assert(offsetof(bt_rec, l3) == 28, "L3 union at 28");
 static_assert(offsetof(bt_rec, l4) == 68, "L4 union at 68");
 static_assert(offsetof(bt_rec, detect_code) == 88, "detector column at 88");
+static_assert(sizeof(bt_tally) == 2304 && offsetof(bt_tally, code) == 40, "bt_tally is 2,304 bytes");
 #endif
 
 #endif /* BEATRICE_GPU_H */

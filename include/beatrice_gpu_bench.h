@@ -75,6 +75,17 @@ int  bt_time_device2(bt_ctx* ctx, const bt_batch* batch, const bt_outputs* out, 
  * from an event pair recorded by their own dispatches. The outputs are those of the last launch. */
 int  bt_time_pass_pack(bt_ctx* ctx, const bt_batch* frames, const uint64_t* select, const bt_pack_opts* opts,
                        const bt_pack_out* out, uint32_t iters, float* ms);
+/* bt_tally_device `iters` times on the context's stream; ms[i] = launch i's two kernels, from an
+ * event pair recorded by their own dispatches. *out is that of the last launch (or their sum,
+ * with BT_TALLY_ACCUMULATE). */
+int  bt_time_tally(bt_ctx* ctx, const uint8_t* decide, uint32_t n, const bt_batch* frames, const void* records,
+                   uint32_t n_cap, uint32_t flags, bt_tally* out, uint32_t iters, float* ms);
+/* What the tally replaces, `iters` times: copy_ms[i] = the n decision bytes copied to pinned host
+ * memory (wall clock, the wait included), scan_ms[i] = the 16-part host scan of
+ * GpuPacketFilter::scanParallel's inner loop over them on the context's host threads (up to 16).
+ * counts (optional, 2 words): packets counted and passed up to the first THROW / HOST code. */
+int  bt_time_tally_host(bt_ctx* ctx, const uint8_t* decide, uint32_t n, uint32_t iters, float* copy_ms,
+                        float* scan_ms, uint64_t* counts);
 /* A device-to-device hipMemcpyAsync of `bytes` on the context's stream, `iters` times, each
  * between an event pair: the ceiling for moving that many bytes on the device. */
 int  bt_time_copy_d2d(bt_ctx* ctx, void* dst, const void* src, uint64_t bytes, uint32_t iters, float* ms);
