@@ -143,6 +143,68 @@ class Tally(ctypes.Structure):
         return cls.from_buffer_copy(bytes(bytearray(_byte_view(buf)[:ctypes.sizeof(cls)])))
 
 
+FANOUT_MAX_QUEUES = 64
+FANOUT_KEY_USER = 0x1        # use FanoutOpts.key; else the RSS verification key
+FANOUT_KEY_SYMMETRIC = 0x2   # the 0x6d5a-repeated key: both directions of a connection hash alike
+FANOUT_RETA_USER = 0x4       # use FanoutOpts.reta (every entry < queues); else reta[i] = i % queues
+FANOUT_L3_ONLY = 0x8         # never hash ports
+FLOW_NONE, FLOW_V4, FLOW_V4_L4, FLOW_V6, FLOW_V6_L4 = range(5)
+FLOW_NAMES = ("none", "ipv4", "ipv4_l4", "ipv6", "ipv6_l4")
+
+
+class FanoutOpts(ctypes.Structure):
+    """bt_fanout_opts: queues (1..64), FANOUT_* flags, a 40-byte key and a 128-entry indirection table."""
+    _fields_ = [("queues", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("key", ctypes.c_uint8 * 40),
+                ("reta", ctypes.c_uint8 * 128)]
+
+    @classmethod
+    def make(cls, queues: int, flags: int = 0, key=None, reta=None) -> "FanoutOpts":
+        """key (40 bytes) sets FANOUT_KEY_USER, reta (128 entries) FANOUT_RETA_USER."""
+        o = cls(queues, flags)
+        if key is not None:
+            o.flags |= FANOUT_KEY_USER
+            o.key[:] = list(bytes(key))
+        if reta is not None:
+            o.flags |= FANOUT_RETA_USER
+            o.reta[:] = [int(x) for x in reta]
+        return o
+
+
+class FanoutResult(ctypes.Structure):
+    """bt_fanout_result (808 B): bt_flow_fanout_device's queue ranges, byte sums and class counts."""
+    _fields_ = [("n", ctypes.c_uint32), ("n_selected", ctypes.c_uint32), ("start", ctypes.c_uint32 * 65),
+                ("pad0", ctypes.c_uint32), ("bytes", ctypes.c_uint64 * 64), ("klass", ctypes.c_uint32 * 5),
+                ("pad1", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        """Plain ints and lists."""
+        out = {k: int(getattr(self, k)) for k in ("n", "n_selected", "pad0", "pad1")}
+        for k in ("start", "bytes", "klass"):
+            out[k] = [int(x) for x in getattr(self, k)]
+        return out
+
+    @classmethod
+    def from_bytes(cls, buf) -> "FanoutResult":
+        """The struct held in 808 downloaded bytes."""
+        return cls.from_buffer_copy(bytes(bytearray(_byte_view(buf)[:ctypes.sizeof(cls)])))
+
+
+class FanoutOut(ctypes.Structure):
+    """bt_fanout_out: device-visible pointers; all but result optional."""
+    _fields_ = [("hash", ctypes.c_void_p), ("queue", ctypes.c_void_p), ("idx", ctypes.c_void_p),
+                ("select_q", ctypes.c_void_p), ("result", ctypes.c_void_p)]
+
+
+def flow_hash_host(frame, opts: "FanoutOpts") -> tuple:
+    """bt_flow_hash_host (host only): (hash, class, queue) of one frame (bytes or a uint8 array)."""
+    a = _byte_view(frame)
+    keep = a if len(a) else np.zeros(1, np.uint8)
+    h, k, q = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+    _check(lib().bt_flow_hash_host(keep.ctypes.data, len(a), ctypes.byref(opts), ctypes.byref(h), ctypes.byref(k),
+                                   ctypes.byref(q)))
+    return h.value, k.value, q.value
+
+
 class PcapInfo(ctypes.Structure):
     """bt_pcap_info: what bt_pcap_index read from a capture file's global header."""
     _fields_ = [("magic", ctypes.c_uint32), ("swapped", ctypes.c_uint32), ("nanosecond", ctypes.c_uint32),
@@ -252,6 +314,7 @@ EXPORTS = [
     "bt_usable_cpus", "bt_extract_host", "bt_filter_dfa_pool", "bt_group_split_plan",
     "bt_group_host_parallel", "bt_pass_pack_device", "bt_pcap_index", "bt_pcap_filter", "bt_time_pass_pack",
     "bt_time_copy_d2d", "bt_tally_device", "bt_time_tally", "bt_time_tally_host",
+    "bt_flow_fanout_device", "bt_flow_hash_host", "bt_time_fanout", "bt_time_fanout_host",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -290,6 +353,13 @@ def lib() -> ctypes.CDLL:
         "bt_tally_device": (ctypes.c_int, [vp, vp, u32, ctypes.POINTER(Batch), vp, u32, u32, vp, vp]),
         "bt_time_tally": (ctypes.c_int, [vp, vp, u32, ctypes.POINTER(Batch), vp, u32, u32, vp, u32, vp]),
         "bt_time_tally_host": (ctypes.c_int, [vp, vp, u32, u32, vp, vp, vp]),
+        "bt_flow_fanout_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(FanoutOpts),
+                                                 ctypes.POINTER(FanoutOut), vp]),
+        "bt_flow_hash_host": (ctypes.c_int, [vp, u32, ctypes.POINTER(FanoutOpts), ctypes.POINTER(u32),
+                                             ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "bt_time_fanout": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(FanoutOpts),
+                                          ctypes.POINTER(FanoutOut), u32, vp]),
+        "bt_time_fanout_host": (ctypes.c_int, [vp, vp, u32, vp, vp, ctypes.POINTER(FanoutOpts), u32, vp, vp, vp]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -634,6 +704,19 @@ class Context:
         ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
         _check(lib().bt_tally_device(self.h, ptr(decide_ptr), n, ctypes.byref(frames) if frames is not None else None,
                                      ptr(records_ptr), n_cap, flags, ptr(out_ptr), stream))
+
+    def flow_fanout_device(self, batch: Batch, opts: "FanoutOpts", result, select=None, hash=None, queue=None,
+                           idx=None, select_q=None, stream=None):
+        """bt_flow_fanout_device: the packets of `batch` selected by the verdict-layout words at
+        `select` (None = all) fanned out to opts.queues queues by RSS flow hash. result: 808 B
+        (FanoutResult), 8-byte aligned; hash (n u32), queue (n bytes), idx (n u32: the selected
+        indices grouped by queue, ascending inside one) and select_q (queues * ceil(n / 64) words:
+        row q is pass_pack's `select` for queue q) are optional. Pointers are addresses or
+        DeviceBuffers. Asynchronous on `stream`."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        out = FanoutOut(ptr(hash), ptr(queue), ptr(idx), ptr(select_q), ptr(result))
+        _check(lib().bt_flow_fanout_device(self.h, ctypes.byref(batch), ptr(select), ctypes.byref(opts),
+                                           ctypes.byref(out), stream))
 
     def pcap_filter(self, buf):
         """bt_pcap_filter: the classic pcap file in `buf` through the compiled program. Returns

@@ -22,6 +22,7 @@
 #include "bt_device.h"
 #include "bt_pack.h"
 #include "bt_tally.h"
+#include "bt_fanout.h"
 #include "bt_host_pool.h"
 #include "bt_host.h"
 
@@ -107,6 +108,8 @@ struct bt_ctx {
         uint64_t* verdict = nullptr;
         bt::PackChunkSum* pack_sums = nullptr;   // bt_pass_pack_device: chunk sums, then a word per tile
         bt::TallyPartial* tally_parts = nullptr; // bt_tally_device: one partial per chunk
+        uint8_t* fan_parts = nullptr;            // bt_flow_fanout_device: fan_ws_bytes(chunks), partials then 64 words per chunk
+        uint8_t* fan_queue = nullptr;            // ... and a queue byte per packet, for calls without out->queue
         hipStream_t last = nullptr;
         bool lazy = false;             // sync not recorded yet (last is a context stream)
         hipEvent_t sync = nullptr;
@@ -231,6 +234,10 @@ int run_pass_pack(bt_ctx* c, const bt_batch* b, const uint64_t* select, const bt
 // bt_tally_host.cpp (bt_timing.cpp's bt_time_tally times the same launch)
 int run_tally(bt_ctx* c, const uint8_t* decide, uint32_t n, const bt_batch* frames, const void* records, uint32_t n_cap,
               uint32_t flags, bt_tally* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+
+// bt_fanout_host.cpp (bt_timing.cpp's bt_time_fanout times the same launches)
+int run_fanout(bt_ctx* c, const bt_batch* frames, const uint64_t* select, const bt_fanout_opts* opts, const bt_fanout_out* out,
+               hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 
 // bt_extract_host.cpp (bt_timing.cpp's bt_time_extract2 times the same launch)
 int build_table(const bt_field_def* f, uint32_t n, ExTable* t, uint64_t* span_out, bool* never);

@@ -20,6 +20,10 @@ void free_ws(bt_ctx* c) {
         if (w.verdict) (void)hipFree(w.verdict);
         if (w.pack_sums) (void)hipFree(w.pack_sums);
         if (w.tally_parts) (void)hipFree(w.tally_parts);
+        if (w.fan_parts) (void)hipFree(w.fan_parts);
+        if (w.fan_queue) (void)hipFree(w.fan_queue);
+        w.fan_parts = nullptr;
+        w.fan_queue = nullptr;
         w.pack_sums = nullptr;
         w.tally_parts = nullptr;
         w.chunk_sums = nullptr; w.verdict = nullptr; w.last = nullptr; w.lazy = false;
@@ -48,6 +52,8 @@ int ensure_ws(bt_ctx* c, uint32_t n) {
         HIP_TRY(hipMalloc(&w.verdict, (size_t)ntiles * 8));
         HIP_TRY(hipMalloc(&w.pack_sums, (size_t)nchunks * sizeof(PackChunkSum) + (size_t)ntiles * 4));
         HIP_TRY(hipMalloc(&w.tally_parts, (size_t)nchunks * sizeof(TallyPartial)));
+        HIP_TRY(hipMalloc(&w.fan_parts, fan_ws_bytes(nchunks)));
+        HIP_TRY(hipMalloc(&w.fan_queue, (size_t)ntiles * 64));
     }
     for (auto& e : c->ws.main_done)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));

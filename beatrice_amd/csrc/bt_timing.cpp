@@ -119,6 +119,24 @@ int bt_time_tally(bt_ctx* c, const uint8_t* decide, uint32_t n, const bt_batch* 
     return BT_OK;
 }
 
+int bt_time_fanout(bt_ctx* c, const bt_batch* frames, const uint64_t* select, const bt_fanout_opts* opts,
+                   const bt_fanout_out* out, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !frames || !frames->n || !iters || !ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int rc = run_fanout(c, frames, select, opts, out, c->stream, c->timing.tev[2 * i], c->timing.tev[2 * i + 1])) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
 // What the tally replaces: the decision bytes copied to pinned host memory, then the 16-part host
 // scan of GpuPacketFilter::scanParallel's inner loop (counted, passed, rejected per slot, up to
 // the first throw of each part) on the context's host threads.
@@ -171,6 +189,74 @@ int bt_time_tally_host(bt_ctx* c, const uint8_t* decide, uint32_t n, uint32_t it
     }
     (void)hipHostFree(h);
     if (err != hipSuccess) return set_error(BT_E_INTERNAL, "bt_time_tally_host: %s", hipGetErrorString(err));
+    return BT_OK;
+}
+
+// What the fan-out replaces: the ordered pass list copied to pinned host memory, then
+// bt_flow_hash_host's key and hash per passing frame and a stable K-way bucket of the indices, in
+// 16 contiguous parts on the context's host threads (count, prefix, scatter).
+int bt_time_fanout_host(bt_ctx* c, const uint32_t* pass_idx, uint32_t n_pass, const uint8_t* host_base,
+                        const bt_pkt_desc* host_desc, const bt_fanout_opts* opts, uint32_t iters, float* copy_ms,
+                        float* bucket_ms, uint32_t* counts) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !pass_idx || !n_pass || !host_base || !host_desc || !iters || !copy_ms || !bucket_ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty list / zero iterations");
+    uint8_t key[kFanKeyBytes], reta[kFanReta];
+    char why[96];
+    if (!fanout_opts(opts, key, reta, why, sizeof(why))) return set_error(BT_E_INVALID_ARGUMENT, "bt_time_fanout_host: %s", why);
+    const bool l3_only = (opts->flags & BT_FANOUT_L3_ONLY) != 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t* h = nullptr;
+    HIP_TRY(hipHostMalloc(&h, (size_t)n_pass * 4, hipHostMallocDefault));
+    std::memset(h, 0, (size_t)n_pass * 4);   // first touch outside the timed part
+    std::vector<uint8_t> queue(n_pass);
+    std::vector<uint32_t> idx(n_pass);
+    constexpr uint32_t kParts = 16;
+    struct Part { uint32_t count[64] = {}; char pad[64]; };
+    std::vector<Part> parts(kParts);
+    HostPool& pool = pool_of(c);
+    const unsigned T = pool.size();
+    const auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto ms = [](auto a, auto b) { return std::chrono::duration<float, std::milli>(b - a).count(); };
+    hipError_t err = hipSuccess;
+    for (uint32_t it = 0; it < iters && err == hipSuccess; ++it) {
+        const auto t0 = now();
+        err = hipMemcpyAsync(h, pass_idx, (size_t)n_pass * 4, hipMemcpyDeviceToHost, c->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+        const auto t1 = now();
+        parts.assign(kParts, Part{});
+        pool.run([&](unsigned w) {
+                for (uint32_t k = w; k < kParts; k += T) {
+                    const size_t lo = (size_t)n_pass * k / kParts, hi = (size_t)n_pass * (k + 1) / kParts;
+                    for (size_t j = lo; j < hi; ++j) {
+                        const bt_pkt_desc d = host_desc[h[j]];
+                        uint8_t in[kFanInputMax];
+                        uint32_t klass;
+                        const uint32_t nb = flow_key_host(host_base + BT_DESC_OFF(d), BT_DESC_LEN(d), l3_only, in, &klass);
+                        queue[j] = reta[toeplitz_host(key, in, nb) & 127u];
+                        ++parts[k].count[queue[j]];
+                    }
+                }
+            });
+        uint32_t at = 0;   // queue-major, part-minor exclusive scan
+        for (uint32_t q = 0; q < 64u; ++q)
+            for (uint32_t k = 0; k < kParts; ++k) { const uint32_t v = parts[k].count[q]; parts[k].count[q] = at; at += v; }
+        pool.run([&](unsigned w) {
+                for (uint32_t k = w; k < kParts; k += T) {
+                    const size_t lo = (size_t)n_pass * k / kParts, hi = (size_t)n_pass * (k + 1) / kParts;
+                    for (size_t j = lo; j < hi; ++j) idx[parts[k].count[queue[j]]++] = h[j];
+                }
+            });
+        copy_ms[it] = ms(t0, t1);
+        bucket_ms[it] = ms(t1, now());
+    }
+    if (counts) {   // the first index of every queue's range and the list's last entry: so that the result is used
+        for (uint32_t q = 0; q < 64u; ++q) counts[q] = parts[0].count[q];
+        counts[64] = idx[n_pass - 1];
+    }
+    (void)hipHostFree(h);
+    if (err != hipSuccess) return set_error(BT_E_INTERNAL, "bt_time_fanout_host: %s", hipGetErrorString(err));
     return BT_OK;
 }
 

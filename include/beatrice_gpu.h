@@ -81,7 +81,7 @@ extern "C" {
  * built against an older header should check bt_abi_version() >= the version they need.
  * Added within 2 (new entry points only, nothing existing changed; a host that needs them can
  * look the symbols up): bt_filter_resume_device, bt_ring_stage_tpv3_ex, bt_pass_pack_device,
- * bt_pcap_index, bt_pcap_filter, bt_tally_device. */
+ * bt_pcap_index, bt_pcap_filter, bt_tally_device, bt_flow_fanout_device, bt_flow_hash_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -510,6 +510,66 @@ int  bt_tally_device(bt_ctx* ctx, const uint8_t* decide, uint32_t n,
                      const bt_batch* frames,     /* optional: only lengths are read -> bytes[]     */
                      const void* records, uint32_t n_cap,   /* optional -> layer_*[]               */
                      uint32_t flags, bt_tally* out, void* stream);
+
+/* ---- fan-out of a batch to K queues by RSS flow hash ---------------------------------
+ * What a capture pipeline does next with the packets that passed: hand each one to one of K
+ * workers so that a flow stays on one worker (the reference's ThreadPool / PluginManager
+ * shards, PACKET_FANOUT_HASH on ingest), for a batch that stays on the device. The hash is the
+ * Microsoft RSS Toeplitz hash (MSB first) of the flow key under a 40-byte key, and
+ * queue = reta[hash & 127], so a host can reproduce its NIC's queue choice.
+ * The flow key is defined on the bt_rec the parser gives for the frame (the layer walk and its
+ * ok bits, so tagged, QinQ and IP-option frames key on their real addresses and ports):
+ *   ok & BT_L_IPV4: source_ip | destination_ip (BT_FLOW_V4), followed by source_port |
+ *     destination_port in wire order when ok & (BT_L_TCP | BT_L_UDP) and
+ *     (ipv4.flags & 0x3FFF) == 0, neither MF nor a fragment offset (BT_FLOW_V4_L4): every
+ *     fragment of a datagram lands in one queue;
+ *   ok & BT_L_IPV6: the 32 address bytes (BT_FLOW_V6), plus the ports when TCP or UDP parsed
+ *     (BT_FLOW_V6_L4); no extension-header walk, as in the parser;
+ *   ICMP never adds ports, BT_FANOUT_L3_ONLY never hashes ports; anything else is
+ *   BT_FLOW_NONE with hash 0.
+ * `select` has the verdict-word layout (out->verdict of a filter call is one; NULL = all n);
+ * bits at or above n are ignored. Both descriptor formats and fixed stride (frame length
+ * min(stride, 65535) in bytes[]) are taken. Frame bytes are read under the rule of
+ * bt_parse_filter_device: no load outside the 16-B granules of [base, base + bytes), bytes past
+ * `bytes` read as zeros, so the key equals the one from that call's record.
+ * Asynchronous on `stream` (NULL = the context's stream), no host synchronisation, three kernel
+ * launches (two without out->idx; none for n == 0, which still writes *result on the stream), no global atomics: every
+ * output is bit-identical from run to run. No allocation once bt_reserve(n) has been called.
+ * Nothing is written at or past n_selected in idx, past n in hash / queue, or past
+ * queues * ceil(n / 64) words in select_q.
+ * BT_E_INVALID_ARGUMENT: a null context, frames, opts, out or result (or a result that is not
+ * 8-byte aligned), BT_BATCH_PREFIXES / BT_BATCH_LEAN, a batch bt_parse_filter_device refuses,
+ * queues outside 1..64, a reta entry >= queues, both key flags, unknown flag bits. */
+#define BT_FANOUT_MAX_QUEUES 64u
+#define BT_FANOUT_KEY_USER      0x1u  /* use opts->key; else the RSS verification key (6d5a56da 255b0ec2 ... 6a42b73b beac01fa) */
+#define BT_FANOUT_KEY_SYMMETRIC 0x2u  /* the 0x6d5a-repeated key; exclusive with KEY_USER */
+#define BT_FANOUT_RETA_USER     0x4u  /* use opts->reta (every entry < queues); else reta[i] = i % queues */
+#define BT_FANOUT_L3_ONLY       0x8u  /* never hash ports */
+typedef struct bt_fanout_opts { uint32_t queues /*1..64*/, flags; uint8_t key[40]; uint8_t reta[128]; } bt_fanout_opts;
+
+enum { BT_FLOW_NONE = 0, BT_FLOW_V4 = 1, BT_FLOW_V4_L4 = 2, BT_FLOW_V6 = 3, BT_FLOW_V6_L4 = 4 };
+typedef struct bt_fanout_result {      /* 808 B, device-visible, 8-byte aligned */
+    uint32_t n, n_selected;
+    uint32_t start[65];                /* queue q = idx[start[q] .. start[q+1]); start[queues..64] = n_selected */
+    uint32_t pad0;
+    uint64_t bytes[64];                /* selected frames' lengths per queue (min(len, 65535), as the pack) */
+    uint32_t klass[5];                 /* selected packets by BT_FLOW_* */
+    uint32_t pad1;
+} bt_fanout_result;
+typedef struct bt_fanout_out {         /* device-visible; all but result optional */
+    uint32_t* hash;      /* n: the hash of every packet in [0, n), selected or not (0 for BT_FLOW_NONE) */
+    uint8_t*  queue;     /* n: the queue of a selected packet, 0xFF otherwise */
+    uint32_t* idx;       /* n entries: the selected packets' indices grouped by queue, ascending inside a queue */
+    uint64_t* select_q;  /* queues * ceil(n/64) words: row q is a verdict-layout selection of queue q's packets,
+                            usable as-is as bt_pass_pack_device's `select`; bits at or above n are 0 */
+    bt_fanout_result* result;
+} bt_fanout_out;
+int  bt_flow_fanout_device(bt_ctx* ctx, const bt_batch* frames, const uint64_t* select /* NULL = all n */,
+                           const bt_fanout_opts* opts, const bt_fanout_out* out, void* stream);
+/* Host only, no context: the class, hash and queue of one frame of `len` readable bytes (any
+ * output may be NULL). BT_E_INVALID_ARGUMENT: a null frame with len > 0, opts as above. */
+int  bt_flow_hash_host(const uint8_t* frame, uint32_t len, const bt_fanout_opts* opts, uint32_t* hash,
+                       uint32_t* klass, uint32_t* queue);
 
 /* ---- pcap capture files ------------------------------------------------------------
  * Classic pcap (24-B global header, 16-B record headers), link type 1 (Ethernet), in all four

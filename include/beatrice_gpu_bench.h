@@ -86,6 +86,20 @@ int  bt_time_tally(bt_ctx* ctx, const uint8_t* decide, uint32_t n, const bt_batc
  * counts (optional, 2 words): packets counted and passed up to the first THROW / HOST code. */
 int  bt_time_tally_host(bt_ctx* ctx, const uint8_t* decide, uint32_t n, uint32_t iters, float* copy_ms,
                         float* scan_ms, uint64_t* counts);
+/* bt_flow_fanout_device `iters` times on the context's stream; ms[i] = launch i's kernels (keys,
+ * join and, with out->idx, scatter), from an event pair recorded by the first and the last
+ * kernel's own dispatches. The outputs are those of the last launch. */
+int  bt_time_fanout(bt_ctx* ctx, const bt_batch* frames, const uint64_t* select, const bt_fanout_opts* opts,
+                    const bt_fanout_out* out, uint32_t iters, float* ms);
+/* What the fan-out replaces, `iters` times: copy_ms[i] = the n_pass entries of the device's
+ * pass_idx copied to pinned host memory (wall clock, the wait included), bucket_ms[i] =
+ * bt_flow_hash_host's key and hash of every listed frame (host_base / host_desc: the batch in
+ * host memory) and a stable K-way bucket of the indices, in 16 parts on the context's host
+ * threads. counts (optional, 65 words): where part 0 ended in every queue's range, and the last
+ * index written. */
+int  bt_time_fanout_host(bt_ctx* ctx, const uint32_t* pass_idx, uint32_t n_pass, const uint8_t* host_base,
+                         const bt_pkt_desc* host_desc, const bt_fanout_opts* opts, uint32_t iters, float* copy_ms,
+                         float* bucket_ms, uint32_t* counts);
 /* A device-to-device hipMemcpyAsync of `bytes` on the context's stream, `iters` times, each
  * between an event pair: the ceiling for moving that many bytes on the device. */
 int  bt_time_copy_d2d(bt_ctx* ctx, void* dst, const void* src, uint64_t bytes, uint32_t iters, float* ms);
