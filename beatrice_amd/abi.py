@@ -205,6 +205,76 @@ def flow_hash_host(frame, opts: "FanoutOpts") -> tuple:
     return h.value, k.value, q.value
 
 
+FLOWTAB_L3_ONLY = 0x1          # as FANOUT_L3_ONLY: never key on ports
+FLOWTAB_BIDIRECTIONAL = 0x2    # both directions of a conversation are one flow
+FLOW_ID_UNSELECTED = 0xFFFFFFFF   # packet not in `select`
+FLOW_ID_NONE = 0xFFFFFFFE         # selected, FLOW_NONE: no key, not in the table
+FLOW_ID_OVERFLOW = 0xFFFFFFFD     # selected, keyed, the table was full
+
+# numpy view of bt_flow_rec (80 B): key in wire order (v4 src dst [sport dport]; v6 src dst [sport dport])
+FlowRec = np.dtype({
+    "names": ["key", "klass", "pad", "first", "last", "packets", "bytes", "reserved"],
+    "formats": [("u1", 36), "u1", ("u1", 3), "<u4", "<u4", ("<u4", 2), ("<u8", 2), "<u8"],
+    "offsets": [0, 36, 37, 40, 44, 48, 56, 72],
+    "itemsize": 80,
+})
+
+
+class FlowTableOpts(ctypes.Structure):
+    """bt_flow_table_opts: FLOWTAB_* flags, slots (a power of two >= 128; 0 = the smallest >= 2 n), flow_cap."""
+    _fields_ = [("flags", ctypes.c_uint32), ("slots", ctypes.c_uint32), ("flow_cap", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class FlowTableResult(ctypes.Structure):
+    """bt_flow_table_result (72 B): the counts of a flow table call."""
+    _fields_ = [("n", ctypes.c_uint32), ("n_selected", ctypes.c_uint32), ("n_flows", ctypes.c_uint32),
+                ("n_written", ctypes.c_uint32), ("none_packets", ctypes.c_uint32), ("overflow_packets", ctypes.c_uint32),
+                ("slots", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("klass_flows", ctypes.c_uint32 * 5),
+                ("pad", ctypes.c_uint32), ("none_bytes", ctypes.c_uint64), ("keyed_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        """Plain ints and lists."""
+        out = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "klass_flows"}
+        out["klass_flows"] = [int(x) for x in self.klass_flows]
+        return out
+
+    @classmethod
+    def from_bytes(cls, buf) -> "FlowTableResult":
+        """The struct held in 72 downloaded bytes."""
+        return cls.from_buffer_copy(bytes(bytearray(_byte_view(buf)[:ctypes.sizeof(cls)])))
+
+
+class FlowTableOut(ctypes.Structure):
+    """bt_flow_table_out: device-visible pointers; result is required."""
+    _fields_ = [("flow_id", ctypes.c_void_p), ("flows", ctypes.c_void_p), ("result", ctypes.c_void_p)]
+
+
+def flow_table_scratch_bytes(n: int, slots: int = 0) -> int:
+    """bt_flow_table_scratch_bytes (host only): the scratch a flow table call over n packets needs."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_table_scratch_bytes(n, slots, ctypes.byref(b)))
+    return b.value
+
+
+def flow_table_host(data, desc, opts: "FlowTableOpts", select=None, nbytes=None) -> tuple:
+    """bt_flow_table_host (host only): the flow table of the frames desc (packed descriptors) lists
+    in `data`, of which `nbytes` (default: all) are readable. select: verdict-layout words or
+    None. Returns (flow_id [n] u32, flows [n_written] FlowRec, result dict)."""
+    a = _byte_view(data)
+    keep = a if len(a) else np.zeros(1, np.uint8)
+    d = np.ascontiguousarray(desc, np.uint64)
+    n = len(d)
+    sel = None if select is None else np.ascontiguousarray(select, np.uint64)
+    flow_id = np.zeros(max(1, n), np.uint32)
+    flows = np.zeros(max(1, opts.flow_cap), FlowRec)
+    res = FlowTableResult()
+    _check(lib().bt_flow_table_host(keep.ctypes.data, len(a) if nbytes is None else nbytes, d.ctypes.data if n else None, n,
+                                    sel.ctypes.data if sel is not None and len(sel) else None, ctypes.byref(opts),
+                                    flow_id.ctypes.data, flows.ctypes.data if opts.flow_cap else None, ctypes.byref(res)))
+    return flow_id[:n], flows[:res.n_written], res.as_dict()
+
+
 class PcapInfo(ctypes.Structure):
     """bt_pcap_info: what bt_pcap_index read from a capture file's global header."""
     _fields_ = [("magic", ctypes.c_uint32), ("swapped", ctypes.c_uint32), ("nanosecond", ctypes.c_uint32),
@@ -315,6 +385,8 @@ EXPORTS = [
     "bt_group_host_parallel", "bt_pass_pack_device", "bt_pcap_index", "bt_pcap_filter", "bt_time_pass_pack",
     "bt_time_copy_d2d", "bt_tally_device", "bt_time_tally", "bt_time_tally_host",
     "bt_flow_fanout_device", "bt_flow_hash_host", "bt_time_fanout", "bt_time_fanout_host",
+    "bt_flow_table_scratch_bytes", "bt_flow_table_device", "bt_flow_table_host", "bt_time_flow_table",
+    "bt_time_flow_table_host",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -360,6 +432,15 @@ def lib() -> ctypes.CDLL:
         "bt_time_fanout": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(FanoutOpts),
                                           ctypes.POINTER(FanoutOut), u32, vp]),
         "bt_time_fanout_host": (ctypes.c_int, [vp, vp, u32, vp, vp, ctypes.POINTER(FanoutOpts), u32, vp, vp, vp]),
+        "bt_flow_table_scratch_bytes": (ctypes.c_int, [u32, u32, ctypes.POINTER(u64)]),
+        "bt_flow_table_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(FlowTableOpts), vp, u64,
+                                                ctypes.POINTER(FlowTableOut), vp]),
+        "bt_flow_table_host": (ctypes.c_int, [vp, u64, vp, u32, vp, ctypes.POINTER(FlowTableOpts), vp, vp,
+                                              ctypes.POINTER(FlowTableResult)]),
+        "bt_time_flow_table": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(FlowTableOpts), vp, u64,
+                                              ctypes.POINTER(FlowTableOut), u32, vp]),
+        "bt_time_flow_table_host": (ctypes.c_int, [vp, vp, u32, vp, u64, vp, ctypes.POINTER(FlowTableOpts), u32, vp, vp,
+                                                   ctypes.POINTER(FlowTableResult)]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -717,6 +798,18 @@ class Context:
         out = FanoutOut(ptr(hash), ptr(queue), ptr(idx), ptr(select_q), ptr(result))
         _check(lib().bt_flow_fanout_device(self.h, ctypes.byref(batch), ptr(select), ctypes.byref(opts),
                                            ctypes.byref(out), stream))
+
+    def flow_table_device(self, batch: Batch, opts: "FlowTableOpts", scratch, scratch_bytes: int, result, select=None,
+                          flow_id=None, flows=None, stream=None):
+        """bt_flow_table_device: the flow table of the packets of `batch` selected by the
+        verdict-layout words at `select` (None = all). scratch: flow_table_scratch_bytes(n,
+        opts.slots) bytes of device memory, 256-byte aligned; result: 72 B (FlowTableResult),
+        8-byte aligned; flow_id (n u32) is optional, flows (opts.flow_cap FlowRec) optional when
+        flow_cap is 0. Pointers are addresses or DeviceBuffers. Asynchronous on `stream`."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        out = FlowTableOut(ptr(flow_id), ptr(flows), ptr(result))
+        _check(lib().bt_flow_table_device(self.h, ctypes.byref(batch), ptr(select), ctypes.byref(opts), ptr(scratch),
+                                          scratch_bytes, ctypes.byref(out), stream))
 
     def pcap_filter(self, buf):
         """bt_pcap_filter: the classic pcap file in `buf` through the compiled program. Returns

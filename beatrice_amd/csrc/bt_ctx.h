@@ -23,6 +23,7 @@
 #include "bt_pack.h"
 #include "bt_tally.h"
 #include "bt_fanout.h"
+#include "bt_flowtab.h"
 #include "bt_host_pool.h"
 #include "bt_host.h"
 
@@ -238,6 +239,10 @@ int run_tally(bt_ctx* c, const uint8_t* decide, uint32_t n, const bt_batch* fram
 // bt_fanout_host.cpp (bt_timing.cpp's bt_time_fanout times the same launches)
 int run_fanout(bt_ctx* c, const bt_batch* frames, const uint64_t* select, const bt_fanout_opts* opts, const bt_fanout_out* out,
                hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+
+// bt_flowtab_host.cpp (bt_timing.cpp's bt_time_flow_table times the same launches)
+int run_flow_table(bt_ctx* c, const bt_batch* frames, const uint64_t* select, const bt_flow_table_opts* opts, void* scratch,
+                   uint64_t scratch_bytes, const bt_flow_table_out* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 
 // bt_extract_host.cpp (bt_timing.cpp's bt_time_extract2 times the same launch)
 int build_table(const bt_field_def* f, uint32_t n, ExTable* t, uint64_t* span_out, bool* never);

@@ -137,6 +137,65 @@ int bt_time_fanout(bt_ctx* c, const bt_batch* frames, const uint64_t* select, co
     return BT_OK;
 }
 
+int bt_time_flow_table(bt_ctx* c, const bt_batch* frames, const uint64_t* select, const bt_flow_table_opts* opts, void* scratch,
+                       uint64_t scratch_bytes, const bt_flow_table_out* out, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !frames || !frames->n || !iters || !ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int rc = run_flow_table(c, frames, select, opts, scratch, scratch_bytes, out, c->stream, c->timing.tev[2 * i],
+                                    c->timing.tev[2 * i + 1])) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
+// What the flow table replaces: the ordered pass list copied to pinned host memory, then
+// bt_flow_table_host's group-by over the listed frames on the calling thread (a hash map is not
+// split over threads without a merge; the fan-out's 16-thread bucket is the other baseline).
+int bt_time_flow_table_host(bt_ctx* c, const uint32_t* pass_idx, uint32_t n_pass, const uint8_t* host_base, uint64_t host_bytes,
+                            const bt_pkt_desc* host_desc, const bt_flow_table_opts* opts, uint32_t iters, float* copy_ms,
+                            float* table_ms, bt_flow_table_result* last) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !pass_idx || !n_pass || !host_base || !host_desc || !iters || !copy_ms || !table_ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty list / zero iterations");
+    char why[96];
+    uint32_t slots = 0;
+    if (!flowtab_opts(opts, n_pass, &slots, why, sizeof(why))) return set_error(BT_E_INVALID_ARGUMENT, "bt_time_flow_table_host: %s", why);
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t* h = nullptr;
+    HIP_TRY(hipHostMalloc(&h, (size_t)n_pass * 4, hipHostMallocDefault));
+    std::memset(h, 0, (size_t)n_pass * 4);   // first touch outside the timed part
+    std::vector<bt_pkt_desc> listed(n_pass);
+    std::vector<bt_flow_rec> flows(opts->flow_cap);
+    bt_flow_table_result r{};
+    const auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto ms = [](auto a, auto b) { return std::chrono::duration<float, std::milli>(b - a).count(); };
+    hipError_t err = hipSuccess;
+    for (uint32_t it = 0; it < iters && err == hipSuccess; ++it) {
+        const auto t0 = now();
+        err = hipMemcpyAsync(h, pass_idx, (size_t)n_pass * 4, hipMemcpyDeviceToHost, c->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+        const auto t1 = now();
+        for (uint32_t j = 0; j < n_pass; ++j) listed[j] = host_desc[h[j]];
+        flowtab_host(host_base, host_bytes, listed.data(), n_pass, nullptr, opts->flags, slots, opts->flow_cap, nullptr,
+                     flows.data(), &r);
+        copy_ms[it] = ms(t0, t1);
+        table_ms[it] = ms(t1, now());
+    }
+    if (last) *last = r;   // so that the result is used (and can be checked)
+    (void)hipHostFree(h);
+    if (err != hipSuccess) return set_error(BT_E_INTERNAL, "bt_time_flow_table_host: %s", hipGetErrorString(err));
+    return BT_OK;
+}
+
 // What the tally replaces: the decision bytes copied to pinned host memory, then the 16-part host
 // scan of GpuPacketFilter::scanParallel's inner loop (counted, passed, rejected per slot, up to
 // the first throw of each part) on the context's host threads.

@@ -81,7 +81,8 @@ extern "C" {
  * built against an older header should check bt_abi_version() >= the version they need.
  * Added within 2 (new entry points only, nothing existing changed; a host that needs them can
  * look the symbols up): bt_filter_resume_device, bt_ring_stage_tpv3_ex, bt_pass_pack_device,
- * bt_pcap_index, bt_pcap_filter, bt_tally_device, bt_flow_fanout_device, bt_flow_hash_host. */
+ * bt_pcap_index, bt_pcap_filter, bt_tally_device, bt_flow_fanout_device, bt_flow_hash_host,
+ * bt_flow_table_scratch_bytes, bt_flow_table_device, bt_flow_table_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -570,6 +571,78 @@ int  bt_flow_fanout_device(bt_ctx* ctx, const bt_batch* frames, const uint64_t* 
  * output may be NULL). BT_E_INVALID_ARGUMENT: a null frame with len > 0, opts as above. */
 int  bt_flow_hash_host(const uint8_t* frame, uint32_t len, const bt_fanout_opts* opts, uint32_t* hash,
                        uint32_t* klass, uint32_t* queue);
+
+/* ---- per-batch flow table: flow ids and flow records -----------------------------------
+ * Which flows are in this batch, and how many packets and bytes does each carry (the NetFlow /
+ * conntrack view): an exact group-by on the flow key over a device-resident batch. The key and
+ * class of a packet are exactly those of bt_flow_fanout_device (the walk, the fragment rule, no
+ * IPv6 extension headers, the read rule); two packets are one flow when class and key bytes are
+ * equal: keys are compared, never hashes. No Toeplitz key is involved; the table's probe hash
+ * is a fixed function of the key bytes and the class.
+ * BT_FLOWTAB_BIDIRECTIONAL: endpoint A = source address followed by the source port (no port in
+ * the address-only classes), endpoint B the same of the destination, compared as byte strings.
+ * A > B: the stored key has the endpoints swapped and the packet counts in packets[1] /
+ * bytes[1]; A <= B: in [0].
+ * Flows are numbered in order of first appearance: flows[f].first is strictly increasing in f.
+ * flow_id[i] is that number or a BT_FLOW_ID_* sentinel. flows[f] is written for f < flow_cap
+ * only; n_flows is the whole count. Nothing is written at or past n_written in flows or past n
+ * in flow_id.
+ * opts->slots is a power of two >= 128 (0 = the smallest such power of two >= 2 n; n <= 2^30
+ * then). When the keyed flows do not fit, overflow_packets != 0, every other output of the call
+ * is unspecified (but in bounds), and the caller repeats the call with more slots. A table
+ * with exactly as many slots as flows succeeds.
+ * All scratch is the caller's: bt_flow_table_scratch_bytes(n, slots) bytes of device memory,
+ * 256-byte aligned, initialised by the call on the stream; the context's workspace is not used.
+ * Asynchronous on `stream` (NULL = the context's stream), no host synchronisation, no
+ * allocation; n == 0 launches nothing and still writes *result in stream order. Every output
+ * is bit-identical from run to run.
+ * BT_E_INVALID_ARGUMENT, decided before the context or any HIP call: a null frames, opts, out
+ * or result; a result or scratch that is misaligned (8 / 256 bytes; flows 8, flow_id 4);
+ * unknown flag bits; slots not a power of two or below 128; scratch_bytes below the need (or a
+ * null scratch with n > 0); flows == NULL with flow_cap != 0; BT_BATCH_PREFIXES /
+ * BT_BATCH_LEAN; a batch bt_parse_filter_device refuses; then a null context. */
+#define BT_FLOWTAB_L3_ONLY        0x1u   /* as BT_FANOUT_L3_ONLY: never key on ports */
+#define BT_FLOWTAB_BIDIRECTIONAL  0x2u   /* both directions of a conversation are one flow */
+#define BT_FLOW_ID_UNSELECTED 0xFFFFFFFFu /* packet not in `select` */
+#define BT_FLOW_ID_NONE       0xFFFFFFFEu /* selected, BT_FLOW_NONE: no key, not in the table */
+#define BT_FLOW_ID_OVERFLOW   0xFFFFFFFDu /* selected, keyed, the table was full */
+
+typedef struct bt_flow_rec {          /* 80 B */
+    uint8_t  key[36];    /* as the fan-out's hash input: v4 src(4) dst(4) [sport dport];
+                            v6 src(16) dst(16) [sport dport]; wire order; rest zero */
+    uint8_t  klass;      /* BT_FLOW_V4 .. BT_FLOW_V6_L4 */
+    uint8_t  pad[3];     /* 0 */
+    uint32_t first, last;    /* lowest / highest packet index of the flow in the batch */
+    uint32_t packets[2];     /* [0] packets in the key's direction, [1] the reverse (BIDIRECTIONAL only, else 0) */
+    uint64_t bytes[2];       /* frame lengths, min(len, 65535) as the pack and the fan-out */
+    uint64_t reserved;       /* 0 */
+} bt_flow_rec;
+
+typedef struct bt_flow_table_opts { uint32_t flags; uint32_t slots; /* 0 = auto */ uint32_t flow_cap; uint32_t reserved; } bt_flow_table_opts;
+
+typedef struct bt_flow_table_result { /* 72 B, device-visible, 8-byte aligned */
+    uint32_t n, n_selected, n_flows, n_written;   /* n_written = min(n_flows, flow_cap) */
+    uint32_t none_packets, overflow_packets, slots, reserved;
+    uint32_t klass_flows[5];  uint32_t pad;        /* flows by class; [BT_FLOW_NONE] = 0 */
+    uint64_t none_bytes, keyed_bytes;              /* selected frame lengths without / with a key */
+} bt_flow_table_result;
+
+typedef struct bt_flow_table_out {    /* device-visible */
+    uint32_t* flow_id;               /* optional, n entries */
+    bt_flow_rec* flows;              /* optional when flow_cap == 0; flow_cap entries */
+    bt_flow_table_result* result;    /* required */
+} bt_flow_table_out;
+
+/* Host only: the scratch a call over n packets with `slots` (0 = auto) needs. */
+int  bt_flow_table_scratch_bytes(uint32_t n, uint32_t slots, uint64_t* bytes);
+int  bt_flow_table_device(bt_ctx* ctx, const bt_batch* frames, const uint64_t* select /* NULL = all n */,
+                          const bt_flow_table_opts* opts, void* scratch, uint64_t scratch_bytes,
+                          const bt_flow_table_out* out, void* stream);
+/* The same group-by on the calling thread, no context and no device: packed descriptors over
+ * base[0 .. bytes), a byte at or past `bytes` reads as zero. flow_id may be NULL. */
+int  bt_flow_table_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n,
+                        const uint64_t* select, const bt_flow_table_opts* opts, uint32_t* flow_id,
+                        bt_flow_rec* flows, bt_flow_table_result* result);
 
 /* ---- pcap capture files ------------------------------------------------------------
  * Classic pcap (24-B global header, 16-B record headers), link type 1 (Ethernet), in all four

@@ -100,6 +100,18 @@ int  bt_time_fanout(bt_ctx* ctx, const bt_batch* frames, const uint64_t* select,
 int  bt_time_fanout_host(bt_ctx* ctx, const uint32_t* pass_idx, uint32_t n_pass, const uint8_t* host_base,
                          const bt_pkt_desc* host_desc, const bt_fanout_opts* opts, uint32_t iters, float* copy_ms,
                          float* bucket_ms, uint32_t* counts);
+/* bt_flow_table_device `iters` times on the context's stream; ms[i] = launch i's kernels (keys,
+ * insert, firsts, join, rank and, with out->flow_id, emit), from an event pair recorded by the
+ * first and the last kernel's own dispatches. The outputs are those of the last launch. */
+int  bt_time_flow_table(bt_ctx* ctx, const bt_batch* frames, const uint64_t* select, const bt_flow_table_opts* opts,
+                        void* scratch, uint64_t scratch_bytes, const bt_flow_table_out* out, uint32_t iters, float* ms);
+/* What the flow table replaces, `iters` times: copy_ms[i] = the n_pass entries of the device's
+ * pass_idx copied to pinned host memory (wall clock, the wait included), table_ms[i] =
+ * bt_flow_table_host over the listed frames (host_base[0 .. host_bytes) / host_desc: the batch
+ * in host memory) on the calling thread. last (optional): the last iteration's result. */
+int  bt_time_flow_table_host(bt_ctx* ctx, const uint32_t* pass_idx, uint32_t n_pass, const uint8_t* host_base,
+                             uint64_t host_bytes, const bt_pkt_desc* host_desc, const bt_flow_table_opts* opts,
+                             uint32_t iters, float* copy_ms, float* table_ms, bt_flow_table_result* last);
 /* A device-to-device hipMemcpyAsync of `bytes` on the context's stream, `iters` times, each
  * between an event pair: the ceiling for moving that many bytes on the device. */
 int  bt_time_copy_d2d(bt_ctx* ctx, void* dst, const void* src, uint64_t bytes, uint32_t iters, float* ms);
