@@ -275,6 +275,155 @@ def flow_table_host(data, desc, opts: "FlowTableOpts", select=None, nbytes=None)
     return flow_id[:n], flows[:res.n_written], res.as_dict()
 
 
+FLOW_ID_EXPIRED = 0xFFFFFFFB      # remap[] of an expire: the flow was removed
+FLOW_TRACK_MAGIC = 0x4B525446
+
+# numpy view of bt_flow_track_rec (104 B): record f of a tracker state is flow number f
+FlowTrackRec = np.dtype({
+    "names": ["key", "klass", "pad", "first_batch", "last_batch", "first", "last", "packets", "bytes", "first_ts", "last_ts"],
+    "formats": [("u1", 36), "u1", ("u1", 3), "<u4", "<u4", "<u4", "<u4", ("<u8", 2), ("<u8", 2), "<u8", "<u8"],
+    "offsets": [0, 36, 37, 40, 44, 48, 52, 56, 72, 88, 96],
+    "itemsize": 104,
+})
+
+
+class _Counts(ctypes.Structure):
+    def as_dict(self) -> dict:
+        """Plain ints (arrays as lists)."""
+        return {k: (int(v) if isinstance(v := getattr(self, k), int) else [int(x) for x in v]) for k, _ in self._fields_}
+
+    @classmethod
+    def from_bytes(cls, buf):
+        """The struct held in downloaded bytes."""
+        return cls.from_buffer_copy(bytes(bytearray(_byte_view(buf)[:ctypes.sizeof(cls)])))
+
+
+class FlowTrackHdr(_Counts):
+    """bt_flow_track_hdr (128 B): the head of a tracker state."""
+    _fields_ = [("magic", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("flow_cap", ctypes.c_uint32), ("slots", ctypes.c_uint32),
+                ("n_flows", ctypes.c_uint32), ("seq", ctypes.c_uint32),
+                ("selected_packets", ctypes.c_uint64), ("keyed_packets", ctypes.c_uint64), ("none_packets", ctypes.c_uint64),
+                ("overflow_packets", ctypes.c_uint64), ("selected_bytes", ctypes.c_uint64), ("keyed_bytes", ctypes.c_uint64),
+                ("none_bytes", ctypes.c_uint64), ("overflow_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 5)]
+
+
+class FlowTrackOpts(ctypes.Structure):
+    """bt_flow_track_opts: FLOWTAB_* flags, flow_cap, slots (0 = the smallest power of two >= max(128, 2 flow_cap))."""
+    _fields_ = [("flags", ctypes.c_uint32), ("flow_cap", ctypes.c_uint32), ("slots", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class FlowTrackSizes(_Counts):
+    """bt_flow_track_sizes: the size of a tracker state and the offsets of its parts."""
+    _fields_ = [("total", ctypes.c_uint64), ("header", ctypes.c_uint64), ("records", ctypes.c_uint64), ("slot_words", ctypes.c_uint64),
+                ("slots", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class FlowTrackUpdate(ctypes.Structure):
+    """bt_flow_track_update: ts (n u64, optional) or the scalar batch_ts."""
+    _fields_ = [("ts", ctypes.c_void_p), ("batch_ts", ctypes.c_uint64)]
+
+
+class FlowTrackResult(_Counts):
+    """bt_flow_track_result (64 B): the counts of an update."""
+    _fields_ = [("n", ctypes.c_uint32), ("n_selected", ctypes.c_uint32), ("none_packets", ctypes.c_uint32),
+                ("batch_flows", ctypes.c_uint32), ("new_flows", ctypes.c_uint32), ("overflow_flows", ctypes.c_uint32),
+                ("overflow_packets", ctypes.c_uint32), ("n_flows", ctypes.c_uint32), ("seq", ctypes.c_uint32),
+                ("status", ctypes.c_uint32), ("keyed_bytes", ctypes.c_uint64), ("none_bytes", ctypes.c_uint64),
+                ("overflow_bytes", ctypes.c_uint64)]
+
+
+class FlowTrackOut(ctypes.Structure):
+    _fields_ = [("flow_id", ctypes.c_void_p), ("result", ctypes.c_void_p)]
+
+
+class FlowTrackExpireResult(_Counts):
+    """bt_flow_track_expire_result (32 B)."""
+    _fields_ = [("n_flows_before", ctypes.c_uint32), ("n_flows", ctypes.c_uint32), ("n_idle", ctypes.c_uint32),
+                ("n_expired", ctypes.c_uint32), ("status", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class FlowTrackExpireOut(ctypes.Structure):
+    _fields_ = [("expired", ctypes.c_void_p), ("expired_cap", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("remap", ctypes.c_void_p), ("result", ctypes.c_void_p)]
+
+
+def flow_track_layout(flow_cap: int, slots: int = 0) -> dict:
+    """bt_flow_track_layout (host only): total bytes, the offsets of header, records and slot words, the resolved slots."""
+    s = FlowTrackSizes()
+    _check(lib().bt_flow_track_layout(flow_cap, slots, ctypes.byref(s)))
+    return s.as_dict()
+
+
+def flow_track_scratch_bytes(n: int) -> int:
+    """bt_flow_track_scratch_bytes (host only): the scratch an update of n packets needs."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_track_scratch_bytes(n, ctypes.byref(b)))
+    return b.value
+
+
+def flow_track_expire_scratch_bytes(flow_cap: int) -> int:
+    """bt_flow_track_expire_scratch_bytes (host only)."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_track_expire_scratch_bytes(flow_cap, ctypes.byref(b)))
+    return b.value
+
+
+def flow_track_parse(state, flow_cap: int | None = None) -> tuple:
+    """(header dict, records [n_flows] FlowTrackRec) of a tracker state's bytes (at least header and records)."""
+    a = _byte_view(state)
+    hdr = FlowTrackHdr.from_bytes(a).as_dict()
+    lay = flow_track_layout(hdr["flow_cap"], hdr["slots"])
+    recs = a[lay["records"]:lay["records"] + 104 * hdr["n_flows"]].copy().view(FlowTrackRec)
+    return hdr, recs
+
+
+class HostFlowTracker:
+    """A tracker state in host memory (bt_flow_track_init_host / _update_host / _expire_host)."""
+
+    def __init__(self, flow_cap: int, flags: int = 0, slots: int = 0):
+        self.layout = flow_track_layout(flow_cap, slots)
+        self.flow_cap = flow_cap
+        raw = np.zeros(self.layout["total"] + 256, np.uint8)
+        at = -raw.ctypes.data % 256
+        self.state = raw[at:at + self.layout["total"]]
+        opts = FlowTrackOpts(flags, flow_cap, slots, 0)
+        _check(lib().bt_flow_track_init_host(self.state.ctypes.data, self.state.nbytes, ctypes.byref(opts)))
+
+    def update(self, data, desc, select=None, ts=None, batch_ts: int = 0, nbytes=None) -> tuple:
+        """One batch (packed descriptors into data). Returns (flow_id [n] u32, result dict)."""
+        a = _byte_view(data)
+        keep = a if len(a) else np.zeros(1, np.uint8)
+        d = np.ascontiguousarray(desc, np.uint64)
+        n = len(d)
+        sel = None if select is None else np.ascontiguousarray(select, np.uint64)
+        t = None if ts is None else np.ascontiguousarray(ts, np.uint64)
+        flow_id = np.zeros(max(1, n), np.uint32)
+        res = FlowTrackResult()
+        upd = FlowTrackUpdate(t.ctypes.data if t is not None and len(t) else None, batch_ts)
+        _check(lib().bt_flow_track_update_host(self.state.ctypes.data, self.state.nbytes, keep.ctypes.data,
+                                               len(a) if nbytes is None else nbytes, d.ctypes.data if n else None, n,
+                                               sel.ctypes.data if sel is not None and len(sel) else None, ctypes.byref(upd),
+                                               flow_id.ctypes.data, ctypes.byref(res)))
+        return flow_id[:n], res.as_dict()
+
+    def expire(self, now: int, idle: int, expired_cap: int | None = None, want_remap: bool = True) -> tuple:
+        """Returns (expired records or None when expired_cap is None, remap [flow_cap] u32 or None, result dict)."""
+        exp = None if expired_cap is None else np.zeros(max(1, expired_cap), FlowTrackRec)
+        remap = np.full(self.flow_cap, 0xEEEEEEEE, np.uint32) if want_remap else None
+        res = FlowTrackExpireResult()
+        out = FlowTrackExpireOut(exp.ctypes.data if exp is not None else None, expired_cap or 0, 0,
+                                 remap.ctypes.data if remap is not None else None, ctypes.addressof(res))
+        _check(lib().bt_flow_track_expire_host(self.state.ctypes.data, self.state.nbytes, now, idle, ctypes.byref(out)))
+        r = res.as_dict()
+        return (None if exp is None else exp[:r["n_expired"]]), remap, r
+
+    def header(self) -> dict:
+        return FlowTrackHdr.from_bytes(self.state).as_dict()
+
+    def records(self) -> np.ndarray:
+        return flow_track_parse(self.state)[1]
+
+
 class PcapInfo(ctypes.Structure):
     """bt_pcap_info: what bt_pcap_index read from a capture file's global header."""
     _fields_ = [("magic", ctypes.c_uint32), ("swapped", ctypes.c_uint32), ("nanosecond", ctypes.c_uint32),
@@ -387,6 +536,10 @@ EXPORTS = [
     "bt_flow_fanout_device", "bt_flow_hash_host", "bt_time_fanout", "bt_time_fanout_host",
     "bt_flow_table_scratch_bytes", "bt_flow_table_device", "bt_flow_table_host", "bt_time_flow_table",
     "bt_time_flow_table_host",
+    "bt_flow_track_layout", "bt_flow_track_scratch_bytes", "bt_flow_track_expire_scratch_bytes",
+    "bt_flow_track_init_device", "bt_flow_track_update_device", "bt_flow_track_expire_device",
+    "bt_flow_track_init_host", "bt_flow_track_update_host", "bt_flow_track_expire_host", "bt_flow_track_forget",
+    "bt_time_flow_track", "bt_time_flow_track_host",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -441,6 +594,21 @@ def lib() -> ctypes.CDLL:
                                               ctypes.POINTER(FlowTableOut), u32, vp]),
         "bt_time_flow_table_host": (ctypes.c_int, [vp, vp, u32, vp, u64, vp, ctypes.POINTER(FlowTableOpts), u32, vp, vp,
                                                    ctypes.POINTER(FlowTableResult)]),
+        "bt_flow_track_layout": (ctypes.c_int, [u32, u32, ctypes.POINTER(FlowTrackSizes)]),
+        "bt_flow_track_scratch_bytes": (ctypes.c_int, [u32, ctypes.POINTER(u64)]),
+        "bt_flow_track_expire_scratch_bytes": (ctypes.c_int, [u32, ctypes.POINTER(u64)]),
+        "bt_flow_track_init_device": (ctypes.c_int, [vp, vp, u64, ctypes.POINTER(FlowTrackOpts), vp]),
+        "bt_flow_track_update_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(FlowTrackUpdate), vp, u64,
+                                                       ctypes.POINTER(FlowTrackOut), vp]),
+        "bt_flow_track_expire_device": (ctypes.c_int, [vp, vp, u64, u64, vp, u64, ctypes.POINTER(FlowTrackExpireOut), vp]),
+        "bt_flow_track_forget": (ctypes.c_int, [vp]),
+        "bt_flow_track_init_host": (ctypes.c_int, [vp, u64, ctypes.POINTER(FlowTrackOpts)]),
+        "bt_flow_track_update_host": (ctypes.c_int, [vp, u64, vp, u64, vp, u32, vp, ctypes.POINTER(FlowTrackUpdate), vp,
+                                                     ctypes.POINTER(FlowTrackResult)]),
+        "bt_flow_track_expire_host": (ctypes.c_int, [vp, u64, u64, u64, ctypes.POINTER(FlowTrackExpireOut)]),
+        "bt_time_flow_track": (ctypes.c_int, [vp, vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(FlowTrackUpdate), vp, u64,
+                                              ctypes.POINTER(FlowTrackOut), u32, vp]),
+        "bt_time_flow_track_host": (ctypes.c_int, [vp, vp, u32, vp, u64, u64, u32, vp, vp, ctypes.POINTER(FlowTrackResult)]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -810,6 +978,44 @@ class Context:
         out = FlowTableOut(ptr(flow_id), ptr(flows), ptr(result))
         _check(lib().bt_flow_table_device(self.h, ctypes.byref(batch), ptr(select), ctypes.byref(opts), ptr(scratch),
                                           scratch_bytes, ctypes.byref(out), stream))
+
+    def flow_track_init(self, state, state_bytes: int, flow_cap: int, flags: int = 0, slots: int = 0, stream=None):
+        """bt_flow_track_init_device: an empty tracker in the flow_track_layout(flow_cap, slots)["total"]
+        bytes of device memory at `state` (256-byte aligned). flags: FLOWTAB_*, fixed for its life."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        opts = FlowTrackOpts(flags, flow_cap, slots, 0)
+        _check(lib().bt_flow_track_init_device(self.h, ptr(state), state_bytes, ctypes.byref(opts), stream))
+
+    @staticmethod
+    def flow_track_forget(state):
+        """bt_flow_track_forget (host only): the library forgets the tracker at `state`; call it before
+        the memory is freed or reused. It holds 256 states."""
+        _check(lib().bt_flow_track_forget(state.ptr if isinstance(state, DeviceBuffer) else state))
+
+    def flow_track_update(self, state, batch: Batch, scratch, scratch_bytes: int, result, select=None, ts=None,
+                          batch_ts: int = 0, flow_id=None, stream=None):
+        """bt_flow_track_update_device: the packets of `batch` selected by the verdict-layout words at
+        `select` (None = all) merged into the tracker at `state`. scratch: flow_track_scratch_bytes(n)
+        bytes of device memory, 256-byte aligned; result: 64 B (FlowTrackResult), 8-byte aligned; ts:
+        n u64 timestamps on the device, or None for the scalar batch_ts; flow_id (n u32) optional.
+        Pointers are addresses or DeviceBuffers. Asynchronous on `stream`."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        upd = FlowTrackUpdate(ptr(ts), batch_ts)
+        out = FlowTrackOut(ptr(flow_id), ptr(result))
+        _check(lib().bt_flow_track_update_device(self.h, ptr(state), ctypes.byref(batch), ptr(select), ctypes.byref(upd),
+                                                 ptr(scratch), scratch_bytes, ctypes.byref(out), stream))
+
+    def flow_track_expire(self, state, now: int, idle: int, scratch, scratch_bytes: int, result, expired=None,
+                          expired_cap: int = 0, remap=None, stream=None):
+        """bt_flow_track_expire_device: the flows with last_ts <= now and now - last_ts > idle leave the
+        tracker at `state`, in ascending flow number, into expired[:expired_cap] (FlowTrackRec; None:
+        every idle flow is dropped); remap (flow_cap u32, optional): old number -> new number or
+        FLOW_ID_EXPIRED. scratch: flow_track_expire_scratch_bytes(flow_cap) bytes; result: 32 B
+        (FlowTrackExpireResult). Asynchronous on `stream`."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        out = FlowTrackExpireOut(ptr(expired), expired_cap, 0, ptr(remap), ptr(result))
+        _check(lib().bt_flow_track_expire_device(self.h, ptr(state), now, idle, ptr(scratch), scratch_bytes, ctypes.byref(out),
+                                                 stream))
 
     def pcap_filter(self, buf):
         """bt_pcap_filter: the classic pcap file in `buf` through the compiled program. Returns

@@ -244,6 +244,11 @@ int run_fanout(bt_ctx* c, const bt_batch* frames, const uint64_t* select, const 
 int run_flow_table(bt_ctx* c, const bt_batch* frames, const uint64_t* select, const bt_flow_table_opts* opts, void* scratch,
                    uint64_t scratch_bytes, const bt_flow_table_out* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 
+// bt_flowtrack_host.cpp (bt_timing.cpp's bt_time_flow_track times the same launches)
+int run_flow_track_update(bt_ctx* c, void* state, const bt_batch* frames, const uint64_t* select, const bt_flow_track_update* upd,
+                          void* scratch, uint64_t scratch_bytes, const bt_flow_track_out* out, hipStream_t st, hipEvent_t e0,
+                          hipEvent_t e1);
+
 // bt_extract_host.cpp (bt_timing.cpp's bt_time_extract2 times the same launch)
 int build_table(const bt_field_def* f, uint32_t n, ExTable* t, uint64_t* span_out, bool* never);
 int run_extract(bt_ctx* c, const bt_batch* b, const ExTable& t, bool never, const bt_extract_out* o, hipStream_t st,

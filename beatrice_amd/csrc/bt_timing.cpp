@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "bt_ctx.h"
+#include "bt_flowtrack.h"
 #include "bt_hip_util.h"
 
 using namespace bt;
@@ -193,6 +194,61 @@ int bt_time_flow_table_host(bt_ctx* c, const uint32_t* pass_idx, uint32_t n_pass
     if (last) *last = r;   // so that the result is used (and can be checked)
     (void)hipHostFree(h);
     if (err != hipSuccess) return set_error(BT_E_INTERNAL, "bt_time_flow_table_host: %s", hipGetErrorString(err));
+    return BT_OK;
+}
+
+int bt_time_flow_track(bt_ctx* c, void* state, const bt_batch* frames, const uint64_t* select, const bt_flow_track_update* upd,
+                       void* scratch, uint64_t scratch_bytes, const bt_flow_track_out* out, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !frames || !frames->n || !iters || !ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int rc = run_flow_track_update(c, state, frames, select, upd, scratch, scratch_bytes, out, c->stream,
+                                           c->timing.tev[2 * i], c->timing.tev[2 * i + 1])) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
+// What the tracker replaces: a batch's flow records copied to pinned host memory, then merged into
+// a table on the calling thread (tools/pcap_flows.py's per-chunk download and fold, in C++).
+int bt_time_flow_track_host(bt_ctx* c, const bt_flow_rec* flows, uint32_t n_flows, void* host_state, uint64_t state_bytes,
+                            uint64_t batch_ts, uint32_t iters, float* copy_ms, float* merge_ms, bt_flow_track_result* last) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !flows || !n_flows || !iters || !copy_ms || !merge_ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / no flows / zero iterations");
+    char why[160];
+    FkHostState hs{};
+    if (!fk_host_state(host_state, state_bytes, &hs, why, sizeof(why))) return set_error(BT_E_INVALID_ARGUMENT, "bt_time_flow_track_host: %s", why);
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    bt_flow_rec* h = nullptr;
+    HIP_TRY(hipHostMalloc(&h, (size_t)n_flows * sizeof(bt_flow_rec), hipHostMallocDefault));
+    std::memset(static_cast<void*>(h), 0, (size_t)n_flows * sizeof(bt_flow_rec));   // first touch outside the timed part
+    bt_flow_table_result fr{};
+    fr.n_flows = n_flows;
+    bt_flow_track_result r{};
+    const auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto ms = [](auto a, auto b) { return std::chrono::duration<float, std::milli>(b - a).count(); };
+    hipError_t err = hipSuccess;
+    for (uint32_t it = 0; it < iters && err == hipSuccess; ++it) {
+        const auto t0 = now();
+        err = hipMemcpyAsync(h, flows, (size_t)n_flows * sizeof(bt_flow_rec), hipMemcpyDeviceToHost, c->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+        const auto t1 = now();
+        if (err == hipSuccess) fk_merge_host(hs, h, fr, 0u, nullptr, batch_ts, nullptr, &r);
+        copy_ms[it] = ms(t0, t1);
+        merge_ms[it] = ms(t1, now());
+    }
+    if (last) *last = r;   // so that the result is used (and can be checked)
+    (void)hipHostFree(h);
+    if (err != hipSuccess) return set_error(BT_E_INTERNAL, "bt_time_flow_track_host: %s", hipGetErrorString(err));
     return BT_OK;
 }
 

@@ -82,7 +82,10 @@ extern "C" {
  * Added within 2 (new entry points only, nothing existing changed; a host that needs them can
  * look the symbols up): bt_filter_resume_device, bt_ring_stage_tpv3_ex, bt_pass_pack_device,
  * bt_pcap_index, bt_pcap_filter, bt_tally_device, bt_flow_fanout_device, bt_flow_hash_host,
- * bt_flow_table_scratch_bytes, bt_flow_table_device, bt_flow_table_host. */
+ * bt_flow_table_scratch_bytes, bt_flow_table_device, bt_flow_table_host, bt_flow_track_layout,
+ * bt_flow_track_scratch_bytes, bt_flow_track_expire_scratch_bytes, bt_flow_track_init_device,
+ * bt_flow_track_update_device, bt_flow_track_expire_device, bt_flow_track_init_host,
+ * bt_flow_track_update_host, bt_flow_track_expire_host, bt_flow_track_forget. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -643,6 +646,132 @@ int  bt_flow_table_device(bt_ctx* ctx, const bt_batch* frames, const uint64_t* s
 int  bt_flow_table_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n,
                         const uint64_t* select, const bt_flow_table_opts* opts, uint32_t* flow_id,
                         bt_flow_rec* flows, bt_flow_table_result* result);
+
+/* ---- flow tracker: a flow table that lives across batches ---------------------------------
+ * The per-batch table above forgets everything at the end of a call. The tracker keeps the
+ * flows of a whole capture on the device: every batch is merged into a long-lived table by one
+ * asynchronous call, flow numbers stay the same from batch to batch, and a second call ages idle
+ * flows out and exports their records.
+ * The state is one block of the caller's memory, 256-byte aligned, in three parts
+ * (bt_flow_track_layout gives their offsets and the block's size, as a bt_flow_track_sizes):
+ *   a bt_flow_track_hdr (128 B);
+ *   flow_cap records bt_flow_track_rec, dense: record f is flow number f, records at or past
+ *     n_flows are zero;
+ *   `slots` u32 slot words (open addressing: empty, or a flow number). Private: their content is
+ *     not part of the interface and differs between the device and the host form.
+ * slots == 0 resolves to the smallest power of two >= max(128, 2 flow_cap); otherwise it is a
+ * power of two >= max(128, flow_cap): a table loaded to 1.0 is legal. flow_cap is 1 .. 2^31
+ * (slots is a u32; flow numbers stay far below BT_FLOW_ID_EXPIRED), and <= 2^30 with slots == 0.
+ * flags: BT_FLOWTAB_L3_ONLY, BT_FLOWTAB_BIDIRECTIONAL, fixed for the life of the state.
+ *
+ * bt_flow_track_update_device: the batch's flows are those of bt_flow_table_device under the
+ * state's flags, in that order (its kernels run unchanged into the scratch). A flow whose (class,
+ * key) is in the table is added to its record: packets and bytes per direction, last_batch, last
+ * and last_ts = the timestamp of the flow's last packet of the batch in packet order (not the
+ * maximum). The other flows are new: the r-th new flow in batch order gets number n_flows + r
+ * when that is below flow_cap, with first_ts = the timestamp of its first packet; otherwise it is
+ * not inserted, counts in overflow_flows, its packets count in overflow_packets and read
+ * BT_FLOW_ID_OVERFLOW in flow_id. A packet's timestamp is upd->ts[i] (device, n entries, any
+ * unit) or, with ts == NULL, upd->batch_ts. flow_id[i] is the flow's number in the state or
+ * BT_FLOW_ID_UNSELECTED / _NONE / _OVERFLOW. The batch sequence number (hdr.seq, the number of
+ * accepted update calls; a record's first_batch / last_batch; it wraps at 2^32) advances on
+ * every accepted call, n == 0 included. Every output is exact and bit-identical from run to run
+ * (DESIGN.md §4.2e).
+ * bt_flow_track_expire_device: a flow is idle when last_ts <= now && now - last_ts > idle. Idle
+ * flows are removed in ascending flow number and written to expired[0 .. n_expired); with
+ * expired != NULL at most expired_cap of them are removed per call and the others stay (nothing
+ * is lost), with expired == NULL every idle flow is dropped. The flows that stay keep their order
+ * and are renumbered densely; remap[old] (optional, written for old < n_flows_before) is the new
+ * number or BT_FLOW_ID_EXPIRED. A removed key that appears again is a new flow at the end.
+ * Both calls are asynchronous on `stream` (NULL = the context's), allocate nothing, never
+ * synchronise and never read the device: n_flows lives in the state only. That is why the
+ * library remembers flags, flow_cap and slots of every state bt_flow_track_init_device has
+ * initialised in this process, by address, and the later calls take them from there. The table
+ * holds 256 states: initialising an address again replaces its entry, bt_flow_track_forget(state)
+ * (host only; call it before the memory is freed or reused) frees one, and with 256 other states
+ * known bt_flow_track_init_device returns BT_E_RESOURCE and launches nothing: no live tracker is
+ * ever dropped. A state is known once its init launch has been enqueued. The kernels compare the
+ * remembered values with the state's header; when that is not this tracker's (overwritten, or
+ * initialised on another stream that has not run yet) they leave the state as it is, report
+ * result->status = 1 with every count 0, and an update fills flow_id[0 .. n) with
+ * BT_FLOW_ID_UNSELECTED, so that no per-batch number can pass for a number in the state.
+ * All scratch is the caller's device memory, 256-byte aligned: bt_flow_track_scratch_bytes(n) for
+ * an update of n packets (the per-batch table's scratch at auto slots, n bt_flow_rec, its result,
+ * the local-to-global map and the partials; n <= 2^30), bt_flow_track_expire_scratch_bytes(
+ * flow_cap) for an expire. Calls on one state must be ordered by the caller (one stream).
+ * The host forms do the same over the same layout in host memory, header and records
+ * bit-identical to the device's; they read flags, flow_cap and slots from the header.
+ * BT_E_INVALID_ARGUMENT, decided before the context or any HIP call: null or misaligned
+ * arguments (state and scratch 256 bytes, result / ts / expired 8, flow_id / remap 4); a state
+ * that is not an initialised tracker (device: unknown to this process; host: the header's magic,
+ * or state_bytes below the header's layout); state_bytes below the layout (init); opts the layout
+ * refuses; scratch_bytes below the need; BT_BATCH_PREFIXES / BT_BATCH_LEAN; a batch
+ * bt_parse_filter_device refuses; n above 2^30; expired == NULL with expired_cap != 0; then a
+ * null context. */
+#define BT_FLOW_ID_EXPIRED    0xFFFFFFFBu /* remap[]: the flow was removed by this expire call */
+#define BT_FLOW_TRACK_MAGIC   0x4B525446u /* "FTRK" */
+
+typedef struct bt_flow_track_rec {    /* 104 B, 8-byte aligned */
+    uint8_t  key[36];    /* as bt_flow_rec */
+    uint8_t  klass;
+    uint8_t  pad[3];     /* 0 */
+    uint32_t first_batch, last_batch;   /* sequence numbers of the update calls */
+    uint32_t first, last;               /* packet index inside that batch */
+    uint64_t packets[2];
+    uint64_t bytes[2];
+    uint64_t first_ts, last_ts;
+} bt_flow_track_rec;
+
+typedef struct bt_flow_track_hdr {    /* 128 B, at the state's start */
+    uint32_t magic, flags, flow_cap, slots;
+    uint32_t n_flows, seq;             /* live flows; accepted update calls so far */
+    /* running totals over every update call */
+    uint64_t selected_packets, keyed_packets, none_packets, overflow_packets;   /* overflow is part of keyed */
+    uint64_t selected_bytes, keyed_bytes, none_bytes, overflow_bytes;
+    uint64_t reserved[5];
+} bt_flow_track_hdr;
+
+typedef struct bt_flow_track_opts { uint32_t flags, flow_cap, slots /* 0 = auto */, reserved; } bt_flow_track_opts;
+typedef struct bt_flow_track_sizes { uint64_t total, header, records, slot_words; uint32_t slots, reserved; } bt_flow_track_sizes;
+typedef struct bt_flow_track_update { const uint64_t* ts; /* optional, device, n entries */ uint64_t batch_ts; } bt_flow_track_update;
+
+typedef struct bt_flow_track_result { /* 64 B, device-visible, 8-byte aligned */
+    uint32_t n, n_selected, none_packets, batch_flows;
+    uint32_t new_flows, overflow_flows, overflow_packets, n_flows;   /* n_flows after the call */
+    uint32_t seq, status;             /* this batch's sequence number; 0, or 1: not this tracker's state, nothing done */
+    uint64_t keyed_bytes, none_bytes, overflow_bytes;
+} bt_flow_track_result;
+typedef struct bt_flow_track_out { uint32_t* flow_id; /* optional, n */ bt_flow_track_result* result; } bt_flow_track_out;
+
+typedef struct bt_flow_track_expire_result { /* 32 B, device-visible, 8-byte aligned */
+    uint32_t n_flows_before, n_flows, n_idle, n_expired;
+    uint32_t status, reserved[3];
+} bt_flow_track_expire_result;
+typedef struct bt_flow_track_expire_out {
+    bt_flow_track_rec* expired;      /* optional, expired_cap entries */
+    uint32_t expired_cap, reserved;
+    uint32_t* remap;                 /* optional, flow_cap entries */
+    bt_flow_track_expire_result* result;
+} bt_flow_track_expire_out;
+
+/* Host only. */
+int  bt_flow_track_layout(uint32_t flow_cap, uint32_t slots, bt_flow_track_sizes* layout);
+int  bt_flow_track_scratch_bytes(uint32_t n, uint64_t* bytes);
+int  bt_flow_track_expire_scratch_bytes(uint32_t flow_cap, uint64_t* bytes);
+int  bt_flow_track_init_device(bt_ctx* ctx, void* state, uint64_t state_bytes, const bt_flow_track_opts* opts, void* stream);
+int  bt_flow_track_forget(void* state);   /* host only: BT_E_INVALID_ARGUMENT for a state the process does not know */
+int  bt_flow_track_update_device(bt_ctx* ctx, void* state, const bt_batch* frames, const uint64_t* select /* NULL = all n */,
+                                 const bt_flow_track_update* upd, void* scratch, uint64_t scratch_bytes,
+                                 const bt_flow_track_out* out, void* stream);
+int  bt_flow_track_expire_device(bt_ctx* ctx, void* state, uint64_t now, uint64_t idle, void* scratch, uint64_t scratch_bytes,
+                                 const bt_flow_track_expire_out* out, void* stream);
+/* The same on the calling thread over a state in host memory; packed descriptors as bt_flow_table_host. */
+int  bt_flow_track_init_host(void* state, uint64_t state_bytes, const bt_flow_track_opts* opts);
+int  bt_flow_track_update_host(void* state, uint64_t state_bytes, const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc,
+                               uint32_t n, const uint64_t* select, const bt_flow_track_update* upd /* ts: host */,
+                               uint32_t* flow_id, bt_flow_track_result* result);
+int  bt_flow_track_expire_host(void* state, uint64_t state_bytes, uint64_t now, uint64_t idle,
+                               const bt_flow_track_expire_out* out);
 
 /* ---- pcap capture files ------------------------------------------------------------
  * Classic pcap (24-B global header, 16-B record headers), link type 1 (Ethernet), in all four

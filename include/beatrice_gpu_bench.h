@@ -112,6 +112,20 @@ int  bt_time_flow_table(bt_ctx* ctx, const bt_batch* frames, const uint64_t* sel
 int  bt_time_flow_table_host(bt_ctx* ctx, const uint32_t* pass_idx, uint32_t n_pass, const uint8_t* host_base,
                              uint64_t host_bytes, const bt_pkt_desc* host_desc, const bt_flow_table_opts* opts,
                              uint32_t iters, float* copy_ms, float* table_ms, bt_flow_table_result* last);
+/* bt_flow_track_update_device `iters` times on the context's stream into the same state; ms[i] =
+ * call i's kernels (the per-batch table's and find, join, apply and, with out->flow_id, ids), from
+ * an event pair recorded by the first and the last kernel's own dispatches. Every call merges the
+ * batch again: from the second on, every flow of it is found. */
+int  bt_time_flow_track(bt_ctx* ctx, void* state, const bt_batch* frames, const uint64_t* select,
+                        const bt_flow_track_update* upd, void* scratch, uint64_t scratch_bytes,
+                        const bt_flow_track_out* out, uint32_t iters, float* ms);
+/* What the tracker replaces, `iters` times: copy_ms[i] = the n_flows records of a per-batch table
+ * (flows, on the device) copied to pinned host memory (wall clock, the wait included), merge_ms[i]
+ * = those records merged into the host tracker state at host_state (bt_flow_track_init_host's) on
+ * the calling thread, every flow stamped batch_ts. last (optional): the last merge's result. */
+int  bt_time_flow_track_host(bt_ctx* ctx, const bt_flow_rec* flows, uint32_t n_flows, void* host_state,
+                             uint64_t state_bytes, uint64_t batch_ts, uint32_t iters, float* copy_ms, float* merge_ms,
+                             bt_flow_track_result* last);
 /* A device-to-device hipMemcpyAsync of `bytes` on the context's stream, `iters` times, each
  * between an event pair: the ceiling for moving that many bytes on the device. */
 int  bt_time_copy_d2d(bt_ctx* ctx, void* dst, const void* src, uint64_t bytes, uint32_t iters, float* ms);

@@ -3,7 +3,7 @@ class, addresses, ports, packets and bytes per direction, and the first and last
 the file (the NetFlow / conntrack view of a capture).
 
 Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [--bidirectional] [--l3-only]
-                                  [--top N] [--format csv|json] [--chunk-packets N]
+                                  [--top N] [--format csv|json] [--chunk-packets N] [--track [--idle SECONDS] [--flow-cap N]]
   --filter         as tools/pcap_filter.py takes it; only passing packets are counted
   --bidirectional  both directions of a conversation are one flow (BT_FLOWTAB_BIDIRECTIONAL): the
                    listed source is the smaller endpoint, packets_rev / bytes_rev count the other direction
@@ -11,6 +11,14 @@ Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [-
   --top N          the N flows with the most bytes, largest first (default: every flow, by first packet)
   --format         csv (default, with a header line) or json (one object per line)
   --chunk-packets  packets per device batch (default: at most 64 MiB of the file and 1M packets)
+  --track          keep one flow tracker on the device for the whole file (bt_flow_track_update_device): no
+                   download and no merge per chunk, one wait and one read of its header and records at the
+                   end. The output is that of the default path, byte for byte.
+  --idle SECONDS   with --track: after each chunk, the flows whose last packet is more than SECONDS older than
+                   the chunk's last packet (by the pcap record headers' timestamps) age out
+                   (bt_flow_track_expire_device) and are printed at once, the others at the end; a flow that comes
+                   back is a new line. Adds the columns first_ts and last_ts (seconds, with the file's six or nine decimals).
+  --flow-cap N     with --track: room for N flows (default: one per packet of the file)
 The file is taken in chunks of whole records, as tools/pcap_stats.py takes it. Per chunk: with
 filters the filter-only bt_parse_filter_device, then bt_flow_table_device over its verdict words
 (without filters over every packet). Only the 72-byte result and flows[0 .. n_written) come back
@@ -63,6 +71,104 @@ def merge(table: dict, flows: np.ndarray, lo: int):
             v[5] = lo + int(f["last"])   # chunks ascend
 
 
+def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
+    """The --track path: every chunk merged into one tracker on the device. Returns the output lines'
+    dicts in output order and fills totals."""
+    max_n = max((hi - lo for lo, hi in parts), default=1)
+    max_bytes = max((int(off[hi - 1] + ln[hi - 1] - off[lo]) for lo, hi in parts), default=1)
+    cap = a.flow_cap or max(1, len(off))
+    lay = abi.flow_track_layout(cap)
+    need, xneed = abi.flow_track_scratch_bytes(max_n), abi.flow_track_expire_scratch_bytes(cap)
+    unit = 1_000_000_000 if info["nanosecond"] else 1_000_000
+    starts = np.array([lo for lo, _ in parts] + [0], np.int64)
+    timed = a.idle is not None
+    if timed:   # a record's header is the 16 bytes before its data: ts_sec, ts_frac in the file's byte order
+        head = np.stack([data[off - 16 + k] for k in range(8)], axis=1).astype(np.uint64) if len(off) else np.zeros((0, 8), np.uint64)
+        order = (3, 2, 1, 0) if info["swapped"] else (0, 1, 2, 3)
+        word = lambda b: sum(head[:, b + order[k]] << np.uint64(8 * k) for k in range(4))  # noqa: E731
+        ts = word(0) * np.uint64(unit) + word(4)
+    rows = []
+
+    def lines(recs):
+        for f in recs:
+            v = [int(f["packets"][0]), int(f["packets"][1]), int(f["bytes"][0]), int(f["bytes"][1]),
+                 int(starts[f["first_batch"]]) + int(f["first"]), int(starts[f["last_batch"]]) + int(f["last"])]
+            r = describe(int(f["klass"]), f["key"].tobytes(), v)
+            if timed:
+                digits = 9 if info["nanosecond"] else 6   # exact: seconds, then the file's fraction
+                r["first_ts"], r["last_ts"] = (f"{int(f[c]) // unit}.{int(f[c]) % unit:0{digits}d}" for c in ("first_ts", "last_ts"))
+            rows.append(r)
+
+    d_state, d_scratch, d_res = ctx.alloc(lay["total"]), ctx.alloc(need), ctx.alloc(64)
+    d_data = ctx.alloc((max_bytes + 255) // 256 * 256 + 256)
+    d_desc, d_ver = ctx.alloc(max(16, max_n * 8)), ctx.alloc(max(16, (max_n + 63) // 64 * 8))
+    bufs = [d_state, d_scratch, d_res, d_data, d_desc, d_ver]
+    if timed:
+        d_ts, d_xscratch, d_xres, d_exp = ctx.alloc(max(16, max_n * 8)), ctx.alloc(xneed), ctx.alloc(32), ctx.alloc(104 * cap)
+        bufs += [d_ts, d_xscratch, d_xres, d_exp]
+    ctx.reserve(max_n)
+    ctx.flow_track_init(d_state, lay["total"], cap, flags)
+    for lo, hi in parts:
+        n, first = hi - lo, int(off[lo])
+        nbytes = int(off[hi - 1] + ln[hi - 1]) - first
+        d_data.upload(data[first:first + nbytes])   # waits for the context's stream: the last chunk is done
+        d_desc.upload((off[lo:hi] - first).astype(np.uint64) | (ln[lo:hi].astype(np.uint64) << np.uint64(48)))
+        if timed:
+            d_ts.upload(ts[lo:hi])
+        batch = abi.Batch(d_data.ptr, d_desc.ptr, 0, n, max(nbytes, 1), abi.DESC_PACKED, 0)
+        if filters:
+            ctx.run_device(batch, abi.Outputs(None, 0, d_ver.ptr, None, None, None))
+        ctx.flow_track_update(d_state, batch, d_scratch, need, d_res, select=d_ver if filters else None,
+                              ts=d_ts if timed else None)
+        if timed:   # what aged out is printed now: its count and records come back, nothing else
+            ctx.flow_track_expire(d_state, int(ts[hi - 1]), int(a.idle * unit), d_xscratch, xneed, d_xres, expired=d_exp, expired_cap=cap)
+            ctx.synchronize()
+            x = abi.FlowTrackExpireResult.from_bytes(d_xres.download(np.zeros(32, np.uint8))).as_dict()
+            if x["n_expired"]:
+                lines(d_exp.download(np.zeros(104 * x["n_expired"], np.uint8)).view(abi.FlowTrackRec))
+    ctx.synchronize()   # the one wait of the plain --track path
+    hdr = abi.FlowTrackHdr.from_bytes(d_state.download(np.zeros(128, np.uint8))).as_dict()
+    if hdr["overflow_packets"]:
+        raise SystemExit(f"pcap_flows: more than --flow-cap {cap} flows at once")
+    if hdr["n_flows"]:
+        both = d_state.download(np.zeros(lay["records"] + 104 * hdr["n_flows"], np.uint8))
+        lines(both[lay["records"]:].view(abi.FlowTrackRec))
+    totals["selected"], totals["no_key"] = hdr["selected_packets"], hdr["none_packets"]
+    abi.Context.flow_track_forget(d_state)   # before its memory goes back
+    for b in bufs:
+        b.free()
+    return rows
+
+
+def per_chunk(ctx, filters, flags, data, off, ln, parts, max_n, max_bytes, table, totals):
+    """The default path: a per-batch table, a download of its records and a merge by key per chunk."""
+    need = abi.flow_table_scratch_bytes(max_n, 0)
+    d_data = ctx.alloc((max_bytes + 255) // 256 * 256 + 256)
+    d_desc, d_ver = ctx.alloc(max(16, max_n * 8)), ctx.alloc(max(16, (max_n + 63) // 64 * 8))
+    d_scratch, d_flows, d_res = ctx.alloc(need), ctx.alloc(80 * max_n), ctx.alloc(abi.ctypes.sizeof(abi.FlowTableResult))
+    ctx.reserve(max_n)
+    for lo, hi in parts:
+        n, first = hi - lo, int(off[lo])
+        nbytes = int(off[hi - 1] + ln[hi - 1]) - first
+        d_data.upload(data[first:first + nbytes])   # waits for the context's stream: the last chunk is done
+        d_desc.upload((off[lo:hi] - first).astype(np.uint64) | (ln[lo:hi].astype(np.uint64) << np.uint64(48)))
+        batch = abi.Batch(d_data.ptr, d_desc.ptr, 0, n, max(nbytes, 1), abi.DESC_PACKED, 0)
+        if filters:
+            ctx.run_device(batch, abi.Outputs(None, 0, d_ver.ptr, None, None, None))
+        ctx.flow_table_device(batch, abi.FlowTableOpts(flags, 0, n, 0), d_scratch, need, d_res,
+                              select=d_ver if filters else None, flows=d_flows)
+        ctx.synchronize()
+        res = abi.FlowTableResult.from_bytes(d_res.download(np.zeros(d_res.nbytes, np.uint8))).as_dict()
+        if res["overflow_packets"]:   # 2 n slots hold any n flows
+            raise SystemExit("pcap_flows: the flow table overflowed")
+        got = d_flows.download(np.zeros(80 * res["n_written"], np.uint8)) if res["n_written"] else np.zeros(0, np.uint8)
+        merge(table, got.view(abi.FlowRec), lo)   # only the records cross PCIe
+        totals["selected"] += res["n_selected"]
+        totals["no_key"] += res["none_packets"]
+    for b in (d_data, d_desc, d_ver, d_scratch, d_flows, d_res):
+        b.free()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--in", dest="src", required=True)
@@ -73,9 +179,18 @@ def main():
     ap.add_argument("--format", choices=("csv", "json"), default="csv")
     ap.add_argument("--chunk-packets", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--track", action="store_true")
+    ap.add_argument("--idle", type=float, default=None, metavar="SECONDS")
+    ap.add_argument("--flow-cap", type=int, default=0)
     a = ap.parse_args()
     if a.chunk_packets < 0 or a.top < 0:
         raise SystemExit("--chunk-packets / --top: want a positive count")
+    if (a.idle is not None or a.flow_cap) and not a.track:
+        raise SystemExit("--idle / --flow-cap: only with --track")
+    if a.idle is not None and (a.idle < 0 or a.top):
+        raise SystemExit("--idle: want a time in seconds >= 0, and no --top (flows are printed as they age out)")
+    if a.flow_cap < 0:
+        raise SystemExit("--flow-cap: want a positive count")
     filters = [parse_filter(f) for f in a.filter]
     data = np.fromfile(a.src, np.uint8)
     try:
@@ -90,50 +205,31 @@ def main():
     table: dict = {}
     totals = {"packets": int(len(desc)), "selected": 0, "no_key": 0, "chunks": len(parts), "truncated": info["truncated"]}
     ctx = abi.Context(a.device)
+    tracked = None
     try:
         if any(s.kind == K_HOST for s in ctx.compile(filters)):
             raise SystemExit("pcap_flows: a filter the GPU cannot decide (a CUSTOM callback, a PAYLOAD regex outside "
                              "its subset) is in the program")
-        need = abi.flow_table_scratch_bytes(max_n, 0)
-        d_data = ctx.alloc((max_bytes + 255) // 256 * 256 + 256)
-        d_desc, d_ver = ctx.alloc(max(16, max_n * 8)), ctx.alloc(max(16, (max_n + 63) // 64 * 8))
-        d_scratch, d_flows, d_res = ctx.alloc(need), ctx.alloc(80 * max_n), ctx.alloc(abi.ctypes.sizeof(abi.FlowTableResult))
-        ctx.reserve(max_n)
-        for lo, hi in parts:
-            n, first = hi - lo, int(off[lo])
-            nbytes = int(off[hi - 1] + ln[hi - 1]) - first
-            d_data.upload(data[first:first + nbytes])   # waits for the context's stream: the last chunk is done
-            d_desc.upload((off[lo:hi] - first).astype(np.uint64) | (ln[lo:hi].astype(np.uint64) << np.uint64(48)))
-            batch = abi.Batch(d_data.ptr, d_desc.ptr, 0, n, max(nbytes, 1), abi.DESC_PACKED, 0)
-            if filters:
-                ctx.run_device(batch, abi.Outputs(None, 0, d_ver.ptr, None, None, None))
-            ctx.flow_table_device(batch, abi.FlowTableOpts(flags, 0, n, 0), d_scratch, need, d_res,
-                                  select=d_ver if filters else None, flows=d_flows)
-            ctx.synchronize()
-            res = abi.FlowTableResult.from_bytes(d_res.download(np.zeros(d_res.nbytes, np.uint8))).as_dict()
-            if res["overflow_packets"]:   # 2 n slots hold any n flows
-                raise SystemExit("pcap_flows: the flow table overflowed")
-            got = d_flows.download(np.zeros(80 * res["n_written"], np.uint8)) if res["n_written"] else np.zeros(0, np.uint8)
-            merge(table, got.view(abi.FlowRec), lo)   # only the records cross PCIe
-            totals["selected"] += res["n_selected"]
-            totals["no_key"] += res["none_packets"]
-        for b in (d_data, d_desc, d_ver, d_scratch, d_flows, d_res):
-            b.free()
+        if a.track:
+            tracked = track(a, ctx, filters, flags, data, info, off, ln, parts, totals)
+        else:
+            per_chunk(ctx, filters, flags, data, off, ln, parts, max_n, max_bytes, table, totals)
     except abi.BtError as e:
         raise SystemExit(f"pcap_flows: {e}")
     finally:
         ctx.close()
-    rows = [describe(k[0], k[1], v) for k, v in table.items()]   # insertion order: by first packet
+    rows = [describe(k[0], k[1], v) for k, v in table.items()] if tracked is None else tracked   # insertion order: by first packet
+    columns = COLUMNS + (("first_ts", "last_ts") if a.idle is not None else ())
     if a.top:
         rows = sorted(rows, key=lambda r: (-(r["bytes"] + r["bytes_rev"]), r["first"]))[:a.top]
     if a.format == "csv":
-        print(",".join(COLUMNS))
+        print(",".join(columns))
         for r in rows:
-            print(",".join("" if r[c] is None else str(r[c]) for c in COLUMNS))
+            print(",".join("" if r[c] is None else str(r[c]) for c in columns))
     else:
         for r in rows:
             print(json.dumps(r))
-    totals["flows"] = len(table)
+    totals["flows"] = len(table) if tracked is None else len(tracked)
     print(json.dumps(totals), file=sys.stderr)
 
 
