@@ -423,6 +423,88 @@ class HostFlowTracker:
     def records(self) -> np.ndarray:
         return flow_track_parse(self.state)[1]
 
+    def tcp_table(self) -> np.ndarray:
+        """The tracker's TCP side table (flow_cap FlowTcpRec, zero), made on first use."""
+        if getattr(self, "tcp", None) is None:
+            self.tcp = np.zeros(self.flow_cap, FlowTcpRec)
+        return self.tcp
+
+    def tcp_update(self, data, desc, flow_id, nbytes=None) -> dict:
+        """bt_flow_tcp_update_host over the batch update() numbered (flow_id: what it returned), under the
+        state's flags, into tcp_table(). Returns the result dict."""
+        return flow_tcp_update_host(data, desc, flow_id, self.header()["flags"], self.tcp_table(), nbytes)
+
+    def expire_tcp(self, now: int, idle: int, closed_idle: int, expired_cap: int | None = None, want_remap: bool = True) -> tuple:
+        """bt_flow_track_expire_tcp_host with tcp_table(). Returns (expired records or None, their side
+        records or None, remap [flow_cap] u32 or None, result dict)."""
+        exp = None if expired_cap is None else np.zeros(max(1, expired_cap), FlowTrackRec)
+        exp_tcp = None if expired_cap is None else np.zeros(max(1, expired_cap), FlowTcpRec)
+        remap = np.full(self.flow_cap, 0xEEEEEEEE, np.uint32) if want_remap else None
+        res = FlowTrackExpireResult()
+        out = FlowTrackExpireOut(exp.ctypes.data if exp is not None else None, expired_cap or 0, 0,
+                                 remap.ctypes.data if remap is not None else None, ctypes.addressof(res))
+        x = FlowTrackExpireTcp(self.tcp_table().ctypes.data, exp_tcp.ctypes.data if exp_tcp is not None else None, closed_idle)
+        _check(lib().bt_flow_track_expire_tcp_host(self.state.ctypes.data, self.state.nbytes, now, idle, ctypes.byref(x),
+                                                   ctypes.byref(out)))
+        r = res.as_dict()
+        ne = r["n_expired"]
+        return (None if exp is None else exp[:ne]), (None if exp_tcp is None else exp_tcp[:ne]), remap, r
+
+
+# TCP flag bits (byte 13 of the TCP header) and the states bt_flow_tcp_state gives
+TCPF_FIN, TCPF_SYN, TCPF_RST, TCPF_PSH, TCPF_ACK = 0x01, 0x02, 0x04, 0x08, 0x10
+TCP_NONE, TCP_OPENING, TCP_ESTABLISHED, TCP_CLOSING, TCP_CLOSED, TCP_RESET, TCP_MIDSTREAM = range(7)
+TCP_STATE_NAMES = ("none", "opening", "established", "closing", "closed", "reset", "midstream")
+
+# numpy view of bt_flow_tcp_rec (16 B): record f of a side table belongs to flow number f
+FlowTcpRec = np.dtype({
+    "names": ["flags", "pad", "syn_packets", "fin_packets", "rst_packets"],
+    "formats": [("u1", 2), ("u1", 2), "<u4", "<u4", "<u4"],
+    "offsets": [0, 2, 4, 8, 12],
+    "itemsize": 16,
+})
+
+
+class FlowTcpResult(_Counts):
+    """bt_flow_tcp_result (32 B): the counts of a side table update."""
+    _fields_ = [("n", ctypes.c_uint32), ("tcp_packets", ctypes.c_uint32), ("syn_packets", ctypes.c_uint32),
+                ("fin_packets", ctypes.c_uint32), ("rst_packets", ctypes.c_uint32), ("bad_ids", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+class FlowTrackExpireTcp(ctypes.Structure):
+    """bt_flow_track_expire_tcp (24 B): the side table, where expired side records go, closed_idle."""
+    _fields_ = [("tcp", ctypes.c_void_p), ("expired_tcp", ctypes.c_void_p), ("closed_idle", ctypes.c_uint64)]
+
+
+def flow_tcp_state(flags_fwd: int, flags_rev: int, table_flags: int = 0) -> int:
+    """bt_flow_tcp_state (host only, pure): a TCP_* state from the two flag unions; not a sequence-checked machine."""
+    return lib().bt_flow_tcp_state(flags_fwd, flags_rev, table_flags)
+
+
+def flow_tcp_update_host(data, desc, flow_id, table_flags: int, tcp: np.ndarray, nbytes=None) -> dict:
+    """bt_flow_tcp_update_host (host only): the frames desc (packed descriptors) lists in `data`, numbered
+    by flow_id, added to the side table `tcp` (FlowTcpRec, in place). Returns the result dict."""
+    a = _byte_view(data)
+    keep = a if len(a) else np.zeros(1, np.uint8)
+    d = np.ascontiguousarray(desc, np.uint64)
+    n = len(d)
+    ids = np.ascontiguousarray(flow_id, np.uint32)
+    if len(ids) != n or tcp.dtype != FlowTcpRec or not tcp.flags["C_CONTIGUOUS"]:
+        raise ValueError("flow_tcp_update_host: one flow_id per descriptor and a contiguous FlowTcpRec table")
+    res = FlowTcpResult()
+    _check(lib().bt_flow_tcp_update_host(keep.ctypes.data, len(a) if nbytes is None else nbytes, d.ctypes.data if n else None, n,
+                                         ids.ctypes.data if n else None, table_flags, tcp.ctypes.data if len(tcp) else None,
+                                         len(tcp), ctypes.addressof(res)))
+    return res.as_dict()
+
+
+def flow_track_expire_tcp_scratch_bytes(flow_cap: int) -> int:
+    """bt_flow_track_expire_tcp_scratch_bytes (host only)."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_track_expire_tcp_scratch_bytes(flow_cap, ctypes.byref(b)))
+    return b.value
+
 
 class PcapInfo(ctypes.Structure):
     """bt_pcap_info: what bt_pcap_index read from a capture file's global header."""
@@ -540,6 +622,8 @@ EXPORTS = [
     "bt_flow_track_init_device", "bt_flow_track_update_device", "bt_flow_track_expire_device",
     "bt_flow_track_init_host", "bt_flow_track_update_host", "bt_flow_track_expire_host", "bt_flow_track_forget",
     "bt_time_flow_track", "bt_time_flow_track_host",
+    "bt_flow_tcp_update_device", "bt_flow_tcp_update_host", "bt_flow_tcp_state", "bt_time_flow_tcp",
+    "bt_flow_track_expire_tcp_scratch_bytes", "bt_flow_track_expire_tcp_device", "bt_flow_track_expire_tcp_host",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -609,6 +693,15 @@ def lib() -> ctypes.CDLL:
         "bt_time_flow_track": (ctypes.c_int, [vp, vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(FlowTrackUpdate), vp, u64,
                                               ctypes.POINTER(FlowTrackOut), u32, vp]),
         "bt_time_flow_track_host": (ctypes.c_int, [vp, vp, u32, vp, u64, u64, u32, vp, vp, ctypes.POINTER(FlowTrackResult)]),
+        "bt_flow_tcp_update_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, u32, vp, u32, vp, vp]),
+        "bt_flow_tcp_update_host": (ctypes.c_int, [vp, u64, vp, u32, vp, u32, vp, u32, vp]),
+        "bt_flow_tcp_state": (ctypes.c_int, [u32, u32, u32]),
+        "bt_time_flow_tcp": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, u32, vp, u32, vp, u32, vp]),
+        "bt_flow_track_expire_tcp_scratch_bytes": (ctypes.c_int, [u32, ctypes.POINTER(u64)]),
+        "bt_flow_track_expire_tcp_device": (ctypes.c_int, [vp, vp, u64, u64, ctypes.POINTER(FlowTrackExpireTcp), vp, u64,
+                                                           ctypes.POINTER(FlowTrackExpireOut), vp]),
+        "bt_flow_track_expire_tcp_host": (ctypes.c_int, [vp, u64, u64, u64, ctypes.POINTER(FlowTrackExpireTcp),
+                                                         ctypes.POINTER(FlowTrackExpireOut)]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -1016,6 +1109,29 @@ class Context:
         out = FlowTrackExpireOut(ptr(expired), expired_cap, 0, ptr(remap), ptr(result))
         _check(lib().bt_flow_track_expire_device(self.h, ptr(state), now, idle, ptr(scratch), scratch_bytes, ctypes.byref(out),
                                                  stream))
+
+    def flow_tcp_update(self, batch: Batch, flow_id, table_flags: int, tcp, flow_cap: int, result, stream=None):
+        """bt_flow_tcp_update_device: the TCP packets of `batch` add their flags byte to the side table
+        `tcp` (flow_cap FlowTcpRec on the device, zeroed once by the caller) at their flow number
+        flow_id[i] (n u32 from flow_table_device or flow_track_update under the same table_flags).
+        result: 32 B (FlowTcpResult), 8-byte aligned. Pointers are addresses or DeviceBuffers.
+        Asynchronous on `stream`: enqueue it behind the call that wrote flow_id."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        _check(lib().bt_flow_tcp_update_device(self.h, ctypes.byref(batch), ptr(flow_id), table_flags, ptr(tcp), flow_cap,
+                                               ptr(result), stream))
+
+    def flow_track_expire_tcp(self, state, now: int, idle: int, closed_idle: int, tcp, scratch, scratch_bytes: int, result,
+                              expired=None, expired_cap: int = 0, expired_tcp=None, remap=None, stream=None):
+        """bt_flow_track_expire_tcp_device: flow_track_expire with one more way to leave (a flow whose
+        TCP state is closed or reset leaves once now - last_ts > closed_idle), and the side table
+        `tcp` (flow_cap FlowTcpRec) is renumbered with the records; expired_tcp (expired_cap FlowTcpRec,
+        optional) receives the side records of expired[]. scratch:
+        flow_track_expire_tcp_scratch_bytes(flow_cap) bytes. Asynchronous on `stream`."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        out = FlowTrackExpireOut(ptr(expired), expired_cap, 0, ptr(remap), ptr(result))
+        x = FlowTrackExpireTcp(ptr(tcp), ptr(expired_tcp), closed_idle)
+        _check(lib().bt_flow_track_expire_tcp_device(self.h, ptr(state), now, idle, ctypes.byref(x), ptr(scratch), scratch_bytes,
+                                                     ctypes.byref(out), stream))
 
     def pcap_filter(self, buf):
         """bt_pcap_filter: the classic pcap file in `buf` through the compiled program. Returns

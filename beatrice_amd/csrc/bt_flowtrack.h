@@ -12,6 +12,7 @@
 
 #include "beatrice_gpu.h"
 #include "bt_flowtab.h"
+#include "bt_flowtcp.h"
 
 #ifdef __HIPCC__
 #define BT_FK_HD __host__ __device__
@@ -140,6 +141,31 @@ struct FlowexpArgs {              // the expire kernels'
 
 BT_FK_HD inline bool fk_is_idle(uint64_t last_ts, uint64_t now, uint64_t idle) { return last_ts <= now && now - last_ts > idle; }
 
+// The TCP-aware expire (bt_flow_track_expire_tcp_*): the plain expire's arguments and the side table.
+struct FlowexpTcpArgs : FlowexpArgs {
+    bt_flow_tcp_rec* tcp;          // the state's side table, flow_cap records
+    bt_flow_tcp_rec* tmp_tcp;      // scratch, flow_cap records
+    bt_flow_tcp_rec* expired_tcp;  // optional, beside expired[]
+    uint64_t closed_idle;
+};
+
+// Does a flow leave under the TCP-aware expire? Idle, or closed / reset and idle by closed_idle.
+BT_FK_HD inline bool fk_tcp_leaves(uint64_t last_ts, const bt_flow_tcp_rec& t, uint32_t flags, uint64_t now, uint64_t idle,
+                                   uint64_t closed_idle) {
+    if (fk_is_idle(last_ts, now, idle)) return true;
+    const int s = flowtcp_state(t.flags[0], t.flags[1], flags);
+    return (s == BT_TCP_CLOSED || s == BT_TCP_RESET) && fk_is_idle(last_ts, now, closed_idle);
+}
+
+struct FxTcpLayout { uint64_t tmp_tcp, total; };   // the plain expire's scratch, then flow_cap side records
+
+inline FxTcpLayout fx_tcp_scratch(uint32_t flow_cap) {
+    FxTcpLayout l{};
+    l.tmp_tcp = fx_scratch(flow_cap).total;
+    l.total = l.tmp_tcp + ft_round((uint64_t)flow_cap * sizeof(bt_flow_tcp_rec));
+    return l;
+}
+
 // The checks of bt_flow_track_init_device / _init_host on everything but the context.
 inline bool flowtrack_init_args(const void* state, uint64_t state_bytes, const bt_flow_track_opts* opts, bt_flow_track_sizes* l,
                                 char* why, size_t cap) {
@@ -246,6 +272,38 @@ inline bool flowtrack_expire_args(const FkShadow* sh, void* state, uint64_t now,
     xa->parts = reinterpret_cast<FxPart*>(s + l.parts);
     xa->ctl = reinterpret_cast<FxCtl*>(s + l.ctl);
     xa->expired = out->expired; xa->remap = out->remap; xa->result = out->result;
+    return true;
+}
+
+// The checks on a bt_flow_track_expire_tcp, for the device and the host form.
+inline bool flowtrack_expire_tcp_x(const bt_flow_track_expire_tcp* x, const bt_flow_track_expire_out* out, char* why, size_t cap) {
+    const auto no = [&](const char* s) { snprintf(why, cap, "%s", s); return false; };
+    if (!x) return no("null x");
+    if (!x->tcp) return no("null tcp");
+    if (reinterpret_cast<uintptr_t>(x->tcp) & 3u) return no("tcp is not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(x->expired_tcp) & 3u) return no("expired_tcp is not 4-byte aligned");
+    if (out && x->expired_tcp && !out->expired) return no("expired_tcp without expired");
+    return true;
+}
+
+// The checks of bt_flow_track_expire_tcp_device on everything but the context.
+inline bool flowtrack_expire_tcp_args(const FkShadow* sh, void* state, uint64_t now, uint64_t idle, const bt_flow_track_expire_tcp* x,
+                                      void* scratch, uint64_t scratch_bytes, const bt_flow_track_expire_out* out, FlowexpTcpArgs* xa,
+                                      char* why, size_t cap) {
+    if (!flowtrack_expire_tcp_x(x, out, why, cap)) return false;
+    FlowexpArgs plain;
+    if (!flowtrack_expire_args(sh, state, now, idle, scratch, scratch_bytes, out, &plain, why, cap)) return false;
+    const FxTcpLayout l = fx_tcp_scratch(sh->flow_cap);
+    if (scratch_bytes < l.total) {
+        snprintf(why, cap, "scratch_bytes %llu below the need %llu", (unsigned long long)scratch_bytes, (unsigned long long)l.total);
+        return false;
+    }
+    *xa = FlowexpTcpArgs{};
+    static_cast<FlowexpArgs&>(*xa) = plain;
+    xa->tcp = x->tcp;
+    xa->tmp_tcp = reinterpret_cast<bt_flow_tcp_rec*>(static_cast<uint8_t*>(scratch) + l.tmp_tcp);
+    xa->expired_tcp = x->expired_tcp;
+    xa->closed_idle = x->closed_idle;
     return true;
 }
 
@@ -393,9 +451,43 @@ inline void fk_expire_host(const FkHostState& s, uint64_t now, uint64_t idle, co
     *out->result = r;
 }
 
+// bt_flow_track_expire_tcp_host's work on a checked state and checked outputs: fk_expire_host with
+// one more way to leave, and the side table moved with the records.
+inline void fk_expire_tcp_host(const FkHostState& s, uint64_t now, uint64_t idle, const bt_flow_track_expire_tcp* x,
+                               const bt_flow_track_expire_out* out) {
+    bt_flow_track_hdr& h = *s.hdr;
+    bt_flow_track_expire_result r{};
+    r.n_flows_before = h.n_flows;
+    uint32_t live = 0;
+    for (uint32_t f = 0; f < h.n_flows; ++f) {
+        const bool leaves = fk_tcp_leaves(s.recs[f].last_ts, x->tcp[f], h.flags, now, idle, x->closed_idle);
+        r.n_idle += leaves ? 1u : 0u;
+        if (leaves && (!out->expired || r.n_expired < out->expired_cap)) {
+            if (out->expired) out->expired[r.n_expired] = s.recs[f];
+            if (x->expired_tcp) x->expired_tcp[r.n_expired] = x->tcp[f];
+            if (out->remap) out->remap[f] = BT_FLOW_ID_EXPIRED;
+            ++r.n_expired;
+            continue;
+        }
+        if (out->remap) out->remap[f] = live;
+        if (live != f) { s.recs[live] = s.recs[f]; x->tcp[live] = x->tcp[f]; }
+        ++live;
+    }
+    if (r.n_expired) {
+        memset(static_cast<void*>(s.recs + live), 0, (size_t)(h.n_flows - live) * sizeof(bt_flow_track_rec));
+        memset(static_cast<void*>(x->tcp + live), 0, (size_t)(h.n_flows - live) * sizeof(bt_flow_tcp_rec));
+        memset(s.slot, 0xFF, (size_t)h.slots * 4u);
+        h.n_flows = live;
+        for (uint32_t f = 0; f < live; ++f) fk_host_claim(s, f);
+    }
+    r.n_flows = live;
+    *out->result = r;
+}
+
 // All launches, asynchronous on `stream`. launch_flowtrack runs behind launch_flowtab (the caller enqueues both).
 int launch_flowtrack_init(const FlowexpArgs& a, void* stream);
 int launch_flowtrack(const FlowtrackArgs& a, void* stream, void* timing_stop = nullptr);
 int launch_flowexpire(const FlowexpArgs& a, void* stream);
+int launch_flowexpire_tcp(const FlowexpTcpArgs& a, void* stream);
 
 }  // namespace bt

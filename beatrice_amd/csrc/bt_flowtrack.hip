@@ -31,7 +31,9 @@
 // leave, the header and *result), _move (the live records to their new place in the scratch, the
 // leaving ones to expired[], remap[]), _back (the scratch back into the state, zeros behind the
 // live records, every slot empty), _claim (the live records claim their slots as above; their keys
-// are distinct). When nothing leaves, the last three change nothing.
+// are distinct). When nothing leaves, the last three change nothing. The TCP-aware expire
+// (bt_flowexpire_tcp_mark, _tcp_move, _tcp_back with the same _scan and _claim) also lets closed and
+// reset connections leave after a shorter time and moves the TCP side table with the records.
 //
 // No lane ever waits for another lane, wave or block: there is no spin, no flag and no look-back,
 // and every loop has a bound in its head; a probe takes at most `slots` steps. Why the outputs are
@@ -451,6 +453,93 @@ __global__ __launch_bounds__(kFkThreads) void bt_flowexpire_claim(FlowexpArgs a)
     claim(a.slot, a.slots, fk_hash(w), f);
 }
 
+// The TCP-aware expire (bt_flow_track_expire_tcp_device): siblings of _mark, _move and _back that
+// also let closed and reset connections leave and move the side table with the records; _scan and
+// _claim run as they are.
+namespace {
+
+__device__ __forceinline__ void tcp_copy(bt_flow_tcp_rec* dst, const bt_flow_tcp_rec* src) {   // 16 B, 4-byte aligned
+    const uint32_t* const q = reinterpret_cast<const uint32_t*>(src);
+    uint32_t* const o = reinterpret_cast<uint32_t*>(dst);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = q[j];
+}
+
+__device__ __forceinline__ bool tcp_leaves(const FlowexpTcpArgs& a, uint32_t f) {   // f < n_flows <= flow_cap
+    return fk_tcp_leaves(a.recs[f].last_ts, a.tcp[f], a.flags, a.now, a.idle, a.closed_idle);
+}
+
+}  // namespace
+
+// X1t: which flows leave, as counts.
+__global__ __launch_bounds__(kFkThreads) void bt_flowexpire_tcp_mark(FlowexpTcpArgs a) {
+    __shared__ uint32_t wn[kFkWaves];
+    if (!hdr_ok(a)) return;
+    const uint32_t nf = a.hdr->n_flows, f0 = blockIdx.x * kFkThreads;
+    if (f0 >= nf) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6, f = f0 + tid;
+    const bool leaves = f < nf && tcp_leaves(a, f);
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(leaves));
+    if (lane == 0) wn[wid] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        FxPart p{};
+#pragma unroll
+        for (uint32_t v = 0; v < kFkWaves; ++v) { p.widle[v] = wn[v]; p.nidle += wn[v]; }
+        a.parts[blockIdx.x] = p;
+    }
+}
+
+// X3t: the first `limit` leaving flows to expired[] / expired_tcp[], the others to their new number in the scratch; remap[].
+__global__ __launch_bounds__(kFkThreads) void bt_flowexpire_tcp_move(FlowexpTcpArgs a) {
+    const FxCtl ctl = *a.ctl;
+    if (!ctl.ok) return;
+    const uint32_t nf = ctl.n_before, f0 = blockIdx.x * kFkThreads;
+    if (f0 >= nf) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6, f = f0 + tid;
+    const bool leaves = f < nf && tcp_leaves(a, f);   // as bt_flowexpire_tcp_mark saw it
+    const uint64_t word = __ballot(leaves);
+    if (f >= nf) return;
+    const FxPart& part = a.parts[blockIdx.x];
+    uint32_t before = part.rel + (uint32_t)__popcll(word & ((1ull << lane) - 1ull));   // leaving flows below f
+    for (uint32_t v = 0; v < wid; ++v) before += part.widle[v];
+    if (leaves && before < ctl.limit) {
+        if (a.expired) rec_copy(a.expired + before, a.recs + f);   // before < limit <= expired_cap
+        if (a.expired_tcp) tcp_copy(a.expired_tcp + before, a.tcp + f);
+        if (a.remap) a.remap[f] = BT_FLOW_ID_EXPIRED;
+        return;
+    }
+    const uint32_t to = f - (before < ctl.limit ? before : ctl.limit);
+    if (ctl.limit) {   // to <= f < flow_cap
+        rec_copy(a.tmp + to, a.recs + f);
+        tcp_copy(a.tmp_tcp + to, a.tcp + f);
+    }
+    if (a.remap) a.remap[f] = to;
+}
+
+// X4t: the live records and their side records back, zeros behind them, every slot empty.
+__global__ __launch_bounds__(kFkThreads) void bt_flowexpire_tcp_back(FlowexpTcpArgs a) {
+    const FxCtl ctl = *a.ctl;
+    if (!ctl.ok || !ctl.limit) return;
+    const uint64_t t = (uint64_t)blockIdx.x * kFkThreads + threadIdx.x, step = (uint64_t)gridDim.x * kFkThreads;
+    u32x4* const q = reinterpret_cast<u32x4*>(a.slot);
+    const uint64_t nq = a.slots / 4u;
+    for (uint64_t x = t; x < nq; x += step) q[x] = u32x4{kFkEmpty, kFkEmpty, kFkEmpty, kFkEmpty};
+    for (uint64_t f = t; f < ctl.n_before; f += step) {   // n_before <= flow_cap
+        uint32_t* const s = reinterpret_cast<uint32_t*>(a.tcp + f);
+        if (f < ctl.n_live) {
+            rec_copy(a.recs + f, a.tmp + f);
+            tcp_copy(a.tcp + f, a.tmp_tcp + f);
+        } else {
+            uint64_t* const o = reinterpret_cast<uint64_t*>(a.recs + f);
+#pragma unroll
+            for (int j = 0; j < 13; ++j) o[j] = 0ull;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s[j] = 0u;
+        }
+    }
+}
+
 namespace {
 
 uint32_t blocks_for(uint64_t items, uint32_t most) {
@@ -492,6 +581,20 @@ int launch_flowexpire(const FlowexpArgs& a, void* stream) {
     launch(bt_flowexpire_back, dim3(blocks_for(quads > a.flow_cap ? quads : a.flow_cap, 4096u)), dim3(kFkThreads), 0, st, nullptr,
            nullptr, a);
     launch(bt_flowexpire_claim, dim3(grid), dim3(kFkThreads), 0, st, nullptr, nullptr, a);
+    return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
+}
+
+int launch_flowexpire_tcp(const FlowexpTcpArgs& a, void* stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t grid = (uint32_t)(((uint64_t)a.flow_cap + kFkThreads - 1u) / kFkThreads);   // flow_cap < 2^32
+    const uint64_t quads = a.slots / 4u;
+    const FlowexpArgs& plain = a;   // _scan and _claim are the plain expire's
+    launch(bt_flowexpire_tcp_mark, dim3(grid), dim3(kFkThreads), 0, st, nullptr, nullptr, a);
+    launch(bt_flowexpire_scan, dim3(1), dim3(kFkJoinThreads), 0, st, nullptr, nullptr, plain);
+    launch(bt_flowexpire_tcp_move, dim3(grid), dim3(kFkThreads), 0, st, nullptr, nullptr, a);
+    launch(bt_flowexpire_tcp_back, dim3(blocks_for(quads > a.flow_cap ? quads : a.flow_cap, 4096u)), dim3(kFkThreads), 0, st, nullptr,
+           nullptr, a);
+    launch(bt_flowexpire_claim, dim3(grid), dim3(kFkThreads), 0, st, nullptr, nullptr, plain);
     return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
 }
 

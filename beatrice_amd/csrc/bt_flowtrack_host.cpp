@@ -162,6 +162,33 @@ extern "C" int bt_flow_track_expire_device(bt_ctx* c, void* state, uint64_t now,
     return BT_OK;
 }
 
+extern "C" int bt_flow_track_expire_tcp_scratch_bytes(uint32_t flow_cap, uint64_t* bytes) {
+    if (!bytes) return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_tcp_scratch_bytes: null bytes");
+    char why[128];
+    bt_flow_track_sizes l{};
+    if (!fk_layout(flow_cap, flow_cap > (1u << 30) ? 1u << 31 : 0u, &l, why, sizeof(why)))
+        return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_tcp_scratch_bytes: %s", why);
+    *bytes = fx_tcp_scratch(flow_cap).total;
+    return BT_OK;
+}
+
+extern "C" int bt_flow_track_expire_tcp_device(bt_ctx* c, void* state, uint64_t now, uint64_t idle, const bt_flow_track_expire_tcp* x,
+                                               void* scratch, uint64_t scratch_bytes, const bt_flow_track_expire_out* out, void* stream) {
+    FlowexpTcpArgs xa;
+    FkShadow sh{};
+    char why[160];
+    const bool known = state && known_state(state, &sh);
+    if (!flowtrack_expire_tcp_args(known ? &sh : nullptr, state, now, idle, x, scratch, scratch_bytes, out, &xa, why, sizeof(why)))
+        return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_tcp_device: %s", why);
+    if (!c) return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_tcp_device: null context");
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = launch_flowexpire_tcp(xa, stream ? stream : c->stream);
+    if (rc) return set_error(rc, "flow tracker kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return BT_OK;
+}
+
 extern "C" int bt_flow_track_init_host(void* state, uint64_t state_bytes, const bt_flow_track_opts* opts) {
     char why[160];
     bt_flow_track_sizes l{};
@@ -194,5 +221,18 @@ extern "C" int bt_flow_track_expire_host(void* state, uint64_t state_bytes, uint
     if (!out->result) return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_host: null result");
     if (!out->expired && out->expired_cap) return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_host: null expired with expired_cap != 0");
     fk_expire_host(hs, now, idle, out);
+    return BT_OK;
+}
+
+extern "C" int bt_flow_track_expire_tcp_host(void* state, uint64_t state_bytes, uint64_t now, uint64_t idle,
+                                             const bt_flow_track_expire_tcp* x, const bt_flow_track_expire_out* out) {
+    char why[160];
+    FkHostState hs{};
+    if (!flowtrack_expire_tcp_x(x, out, why, sizeof(why))) return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_tcp_host: %s", why);
+    if (!fk_host_state(state, state_bytes, &hs, why, sizeof(why))) return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_tcp_host: %s", why);
+    if (!out) return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_tcp_host: null out");
+    if (!out->result) return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_tcp_host: null result");
+    if (!out->expired && out->expired_cap) return set_error(BT_E_INVALID_ARGUMENT, "bt_flow_track_expire_tcp_host: null expired with expired_cap != 0");
+    fk_expire_tcp_host(hs, now, idle, x, out);
     return BT_OK;
 }

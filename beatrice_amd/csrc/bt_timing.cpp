@@ -216,6 +216,25 @@ int bt_time_flow_track(bt_ctx* c, void* state, const bt_batch* frames, const uin
     return BT_OK;
 }
 
+int bt_time_flow_tcp(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, uint32_t table_flags, bt_flow_tcp_rec* tcp,
+                     uint32_t flow_cap, bt_flow_tcp_result* result, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !frames || !frames->n || !iters || !ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int rc = run_flow_tcp(c, frames, flow_id, table_flags, tcp, flow_cap, result, c->stream, c->timing.tev[2 * i],
+                                  c->timing.tev[2 * i + 1])) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
 // What the tracker replaces: a batch's flow records copied to pinned host memory, then merged into
 // a table on the calling thread (tools/pcap_flows.py's per-chunk download and fold, in C++).
 int bt_time_flow_track_host(bt_ctx* c, const bt_flow_rec* flows, uint32_t n_flows, void* host_state, uint64_t state_bytes,

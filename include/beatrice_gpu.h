@@ -85,7 +85,10 @@ extern "C" {
  * bt_flow_table_scratch_bytes, bt_flow_table_device, bt_flow_table_host, bt_flow_track_layout,
  * bt_flow_track_scratch_bytes, bt_flow_track_expire_scratch_bytes, bt_flow_track_init_device,
  * bt_flow_track_update_device, bt_flow_track_expire_device, bt_flow_track_init_host,
- * bt_flow_track_update_host, bt_flow_track_expire_host, bt_flow_track_forget. */
+ * bt_flow_track_update_host, bt_flow_track_expire_host, bt_flow_track_forget,
+ * bt_flow_tcp_update_device, bt_flow_tcp_update_host, bt_flow_tcp_state,
+ * bt_flow_track_expire_tcp_scratch_bytes, bt_flow_track_expire_tcp_device,
+ * bt_flow_track_expire_tcp_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -772,6 +775,89 @@ int  bt_flow_track_update_host(void* state, uint64_t state_bytes, const uint8_t*
                                uint32_t* flow_id, bt_flow_track_result* result);
 int  bt_flow_track_expire_host(void* state, uint64_t state_bytes, uint64_t now, uint64_t idle,
                                const bt_flow_track_expire_out* out);
+
+/* ---- per-flow TCP side table: flag unions, connection state, expiry on close ---------------
+ * What happened on a flow's connection (NetFlow v5 tcp_flags / IPFIX 6, per direction) beside
+ * the flow records above. The table is flow_cap records bt_flow_tcp_rec of the caller's memory;
+ * record f belongs to flow number f of a per-batch table or of a tracker. The caller zeroes it
+ * once (all-zero = nothing seen); there is no init call.
+ * bt_flow_tcp_update_device: packet i contributes when flow_id[i] < flow_cap, the record
+ * bt_parse_filter_device gives for its frame has ok & BT_L_TCP, and, for IPv4,
+ * (ipv4.flags & 0x3FFF) == 0 (the rule under which the flow key takes ports; independent of
+ * BT_FLOWTAB_L3_ONLY). The layers are walked as bt_flow_fanout_device walks them, frame bytes
+ * under its read rule. A contributing packet's value is that record's tcp.flags (byte 13 of the
+ * TCP header): it is ORed into flags[dir] and counts in syn_packets (SYN set and ACK clear),
+ * fin_packets, rst_packets by its bits. dir is the flow table's direction of the packet: 0
+ * without BT_FLOWTAB_BIDIRECTIONAL; with it 1 when the key the table forms under table_flags has
+ * its endpoints swapped. A flow_id that is a BT_FLOW_ID_* sentinel contributes nothing; any
+ * other id >= flow_cap counts in bad_ids and contributes nothing. Nothing is written outside
+ * tcp[0 .. flow_cap) and *result.
+ * flow_id (device, n entries) comes from bt_flow_table_device or bt_flow_track_update_device
+ * under the same table_flags; the caller enqueues this call behind that one and before any
+ * expire of the tracker, on one stream. Asynchronous on `stream` (NULL = the context's), no
+ * allocation, no host synchronisation; n == 0 still writes *result in stream order. Every output
+ * is an OR or an integer sum (counters mod 2^32): bit-identical from run to run.
+ * bt_flow_tcp_update_host: the same on the calling thread, bit-identical; packed descriptors over
+ * base[0 .. bytes), a byte at or past `bytes` reads as zero.
+ * bt_flow_tcp_state: host only and pure. It is a function of the two flag unions, not a
+ * sequence-checked state machine: order-free, hence exact when packets are taken in parallel.
+ * With u = flags_fwd | flags_rev and bidir = table_flags & BT_FLOWTAB_BIDIRECTIONAL, in this order:
+ *   u == 0: BT_TCP_NONE; u & RST: BT_TCP_RESET; FIN in both directions (without bidir: FIN in
+ *   flags_fwd): BT_TCP_CLOSED; u & FIN: BT_TCP_CLOSING; no SYN in u: BT_TCP_MIDSTREAM; SYN in
+ *   both directions (without bidir: SYN and ACK in flags_fwd): BT_TCP_ESTABLISHED; otherwise
+ *   BT_TCP_OPENING.
+ * bt_flow_track_expire_tcp_device is bt_flow_track_expire_device with one more way to leave, and
+ * it carries the side table: a flow leaves when it is idle (last_ts <= now && now - last_ts >
+ * idle), or when its state under the tracker's flags is BT_TCP_CLOSED or BT_TCP_RESET and
+ * last_ts <= now && now - last_ts > closed_idle. n_idle counts that predicate; the order, the
+ * expired_cap truncation, remap, the dense renumbering and status are the plain expire's. x->tcp
+ * (flow_cap records, required) moves with the records: survivor `old` lands at tcp[remap[old]],
+ * entries from the new n_flows up to n_flows_before become zero, entries at or past
+ * n_flows_before are not touched; x->expired_tcp[k] (optional, expired_cap records, needs
+ * out->expired) belongs to expired[k]. Scratch: bt_flow_track_expire_tcp_scratch_bytes(flow_cap),
+ * the plain expire's plus flow_cap side records.
+ * BT_E_INVALID_ARGUMENT, decided before the context or any HIP call: a null frames, flow_id (with
+ * n > 0), tcp (with flow_cap > 0), result or x; misalignment (tcp, expired_tcp and flow_id 4
+ * bytes, result 8); unknown flag bits; expired_tcp without out->expired; BT_BATCH_PREFIXES /
+ * BT_BATCH_LEAN; a batch bt_parse_filter_device refuses; what the plain expire refuses; then a
+ * null context. */
+#define BT_TCPF_FIN 0x01u   /* the wire bits of TCP byte 13 */
+#define BT_TCPF_SYN 0x02u
+#define BT_TCPF_RST 0x04u
+#define BT_TCPF_PSH 0x08u
+#define BT_TCPF_ACK 0x10u
+enum { BT_TCP_NONE = 0, BT_TCP_OPENING = 1, BT_TCP_ESTABLISHED = 2, BT_TCP_CLOSING = 3,
+       BT_TCP_CLOSED = 4, BT_TCP_RESET = 5, BT_TCP_MIDSTREAM = 6 };
+
+typedef struct bt_flow_tcp_rec {      /* 16 B, 4-byte aligned; all-zero = nothing seen */
+    uint8_t  flags[2];                /* OR of the TCP flags byte, per direction as packets[] of the flow record */
+    uint8_t  pad[2];                  /* 0 */
+    uint32_t syn_packets;             /* SYN set and ACK clear; mod 2^32 */
+    uint32_t fin_packets, rst_packets;
+} bt_flow_tcp_rec;
+
+typedef struct bt_flow_tcp_result {   /* 32 B, device-visible, 8-byte aligned */
+    uint32_t n, tcp_packets, syn_packets, fin_packets, rst_packets, bad_ids, reserved[2];
+} bt_flow_tcp_result;
+
+typedef struct bt_flow_track_expire_tcp {   /* 24 B */
+    bt_flow_tcp_rec* tcp;          /* required: the state's side table, flow_cap records */
+    bt_flow_tcp_rec* expired_tcp;  /* optional, expired_cap records; needs out->expired */
+    uint64_t closed_idle;          /* a CLOSED or RESET flow leaves once now - last_ts > closed_idle */
+} bt_flow_track_expire_tcp;
+
+int  bt_flow_tcp_update_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id /* device, n */,
+                               uint32_t table_flags, bt_flow_tcp_rec* tcp, uint32_t flow_cap,
+                               bt_flow_tcp_result* result, void* stream);
+int  bt_flow_tcp_update_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n,
+                             const uint32_t* flow_id, uint32_t table_flags, bt_flow_tcp_rec* tcp, uint32_t flow_cap,
+                             bt_flow_tcp_result* result);
+int  bt_flow_tcp_state(uint32_t flags_fwd, uint32_t flags_rev, uint32_t table_flags);   /* BT_TCP_* */
+int  bt_flow_track_expire_tcp_scratch_bytes(uint32_t flow_cap, uint64_t* bytes);
+int  bt_flow_track_expire_tcp_device(bt_ctx* ctx, void* state, uint64_t now, uint64_t idle, const bt_flow_track_expire_tcp* x,
+                                     void* scratch, uint64_t scratch_bytes, const bt_flow_track_expire_out* out, void* stream);
+int  bt_flow_track_expire_tcp_host(void* state, uint64_t state_bytes, uint64_t now, uint64_t idle,
+                                   const bt_flow_track_expire_tcp* x, const bt_flow_track_expire_out* out);
 
 /* ---- pcap capture files ------------------------------------------------------------
  * Classic pcap (24-B global header, 16-B record headers), link type 1 (Ethernet), in all four

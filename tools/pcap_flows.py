@@ -3,7 +3,8 @@ class, addresses, ports, packets and bytes per direction, and the first and last
 the file (the NetFlow / conntrack view of a capture).
 
 Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [--bidirectional] [--l3-only]
-                                  [--top N] [--format csv|json] [--chunk-packets N] [--track [--idle SECONDS] [--flow-cap N]]
+                                  [--top N] [--format csv|json] [--chunk-packets N]
+                                  [--track [--idle SECONDS] [--flow-cap N] [--tcp [--closed-idle SECONDS]]]
   --filter         as tools/pcap_filter.py takes it; only passing packets are counted
   --bidirectional  both directions of a conversation are one flow (BT_FLOWTAB_BIDIRECTIONAL): the
                    listed source is the smaller endpoint, packets_rev / bytes_rev count the other direction
@@ -19,6 +20,13 @@ Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [-
                    (bt_flow_track_expire_device) and are printed at once, the others at the end; a flow that comes
                    back is a new line. Adds the columns first_ts and last_ts (seconds, with the file's six or nine decimals).
   --flow-cap N     with --track: room for N flows (default: one per packet of the file)
+  --tcp            with --track: a TCP side table beside the tracker (bt_flow_tcp_update_device behind every update).
+                   Adds the columns tcp_flags_fwd and tcp_flags_rev (the union of the TCP flags byte per direction,
+                   hexadecimal), tcp_state (bt_flow_tcp_state: none, opening, established, closing, closed, reset,
+                   midstream; a function of the two unions, not a sequence-checked machine), syn, fin and rst
+                   (packets with SYN and no ACK, with FIN, with RST). Still one wait without --idle.
+  --closed-idle SECONDS  with --tcp and --idle: a closed or reset connection ages out once its last packet is more
+                   than SECONDS older than the chunk's last packet (bt_flow_track_expire_tcp_device)
 The file is taken in chunks of whole records, as tools/pcap_stats.py takes it. Per chunk: with
 filters the filter-only bt_parse_filter_device, then bt_flow_table_device over its verdict words
 (without filters over every packet). Only the 72-byte result and flows[0 .. n_written) come back
@@ -45,6 +53,8 @@ from pcap_stats import MASK48, chunks_of  # noqa: E402
 
 K_HOST = 9   # enum bt_filter_kind
 COLUMNS = ("class", "src", "dst", "sport", "dport", "packets", "bytes", "packets_rev", "bytes_rev", "first", "last")
+TCP_COLUMNS = ("tcp_flags_fwd", "tcp_flags_rev", "tcp_state", "syn", "fin", "rst")
+U64_MAX = (1 << 64) - 1
 
 
 def describe(klass: int, key: bytes, v: list) -> dict:
@@ -89,16 +99,24 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         ts = word(0) * np.uint64(unit) + word(4)
     rows = []
 
-    def lines(recs):
-        for f in recs:
+    def lines(recs, side=None):
+        for k, f in enumerate(recs):
             v = [int(f["packets"][0]), int(f["packets"][1]), int(f["bytes"][0]), int(f["bytes"][1]),
                  int(starts[f["first_batch"]]) + int(f["first"]), int(starts[f["last_batch"]]) + int(f["last"])]
             r = describe(int(f["klass"]), f["key"].tobytes(), v)
             if timed:
                 digits = 9 if info["nanosecond"] else 6   # exact: seconds, then the file's fraction
                 r["first_ts"], r["last_ts"] = (f"{int(f[c]) // unit}.{int(f[c]) % unit:0{digits}d}" for c in ("first_ts", "last_ts"))
+            if side is not None:
+                t = side[k]
+                fwd, rev = int(t["flags"][0]), int(t["flags"][1])
+                r["tcp_flags_fwd"], r["tcp_flags_rev"] = f"0x{fwd:02x}", f"0x{rev:02x}"
+                r["tcp_state"] = abi.TCP_STATE_NAMES[abi.flow_tcp_state(fwd, rev, flags)]
+                r["syn"], r["fin"], r["rst"] = int(t["syn_packets"]), int(t["fin_packets"]), int(t["rst_packets"])
             rows.append(r)
 
+    if a.tcp and timed:
+        xneed = abi.flow_track_expire_tcp_scratch_bytes(cap)
     d_state, d_scratch, d_res = ctx.alloc(lay["total"]), ctx.alloc(need), ctx.alloc(64)
     d_data = ctx.alloc((max_bytes + 255) // 256 * 256 + 256)
     d_desc, d_ver = ctx.alloc(max(16, max_n * 8)), ctx.alloc(max(16, (max_n + 63) // 64 * 8))
@@ -106,6 +124,14 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
     if timed:
         d_ts, d_xscratch, d_xres, d_exp = ctx.alloc(max(16, max_n * 8)), ctx.alloc(xneed), ctx.alloc(32), ctx.alloc(104 * cap)
         bufs += [d_ts, d_xscratch, d_xres, d_exp]
+    if a.tcp:   # the side table, zeroed once; the update's flow ids feed it
+        d_ids, d_tcp, d_tres = ctx.alloc(max(16, max_n * 4)), ctx.alloc(16 * cap), ctx.alloc(32)
+        d_tcp.zero()
+        bufs += [d_ids, d_tcp, d_tres]
+        if timed:
+            d_exp_tcp = ctx.alloc(16 * cap)
+            bufs.append(d_exp_tcp)
+        closed = U64_MAX if a.closed_idle is None else int(a.closed_idle * unit)
     ctx.reserve(max_n)
     ctx.flow_track_init(d_state, lay["total"], cap, flags)
     for lo, hi in parts:
@@ -119,20 +145,28 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         if filters:
             ctx.run_device(batch, abi.Outputs(None, 0, d_ver.ptr, None, None, None))
         ctx.flow_track_update(d_state, batch, d_scratch, need, d_res, select=d_ver if filters else None,
-                              ts=d_ts if timed else None)
+                              ts=d_ts if timed else None, flow_id=d_ids if a.tcp else None)
+        if a.tcp:
+            ctx.flow_tcp_update(batch, d_ids, flags, d_tcp, cap, d_tres)
         if timed:   # what aged out is printed now: its count and records come back, nothing else
-            ctx.flow_track_expire(d_state, int(ts[hi - 1]), int(a.idle * unit), d_xscratch, xneed, d_xres, expired=d_exp, expired_cap=cap)
+            if a.tcp:
+                ctx.flow_track_expire_tcp(d_state, int(ts[hi - 1]), int(a.idle * unit), closed, d_tcp, d_xscratch, xneed, d_xres,
+                                          expired=d_exp, expired_cap=cap, expired_tcp=d_exp_tcp)
+            else:
+                ctx.flow_track_expire(d_state, int(ts[hi - 1]), int(a.idle * unit), d_xscratch, xneed, d_xres, expired=d_exp, expired_cap=cap)
             ctx.synchronize()
             x = abi.FlowTrackExpireResult.from_bytes(d_xres.download(np.zeros(32, np.uint8))).as_dict()
             if x["n_expired"]:
-                lines(d_exp.download(np.zeros(104 * x["n_expired"], np.uint8)).view(abi.FlowTrackRec))
+                lines(d_exp.download(np.zeros(104 * x["n_expired"], np.uint8)).view(abi.FlowTrackRec),
+                      d_exp_tcp.download(np.zeros(16 * x["n_expired"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None)
     ctx.synchronize()   # the one wait of the plain --track path
     hdr = abi.FlowTrackHdr.from_bytes(d_state.download(np.zeros(128, np.uint8))).as_dict()
     if hdr["overflow_packets"]:
         raise SystemExit(f"pcap_flows: more than --flow-cap {cap} flows at once")
     if hdr["n_flows"]:
         both = d_state.download(np.zeros(lay["records"] + 104 * hdr["n_flows"], np.uint8))
-        lines(both[lay["records"]:].view(abi.FlowTrackRec))
+        lines(both[lay["records"]:].view(abi.FlowTrackRec),
+              d_tcp.download(np.zeros(16 * hdr["n_flows"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None)
     totals["selected"], totals["no_key"] = hdr["selected_packets"], hdr["none_packets"]
     abi.Context.flow_track_forget(d_state)   # before its memory goes back
     for b in bufs:
@@ -182,6 +216,8 @@ def main():
     ap.add_argument("--track", action="store_true")
     ap.add_argument("--idle", type=float, default=None, metavar="SECONDS")
     ap.add_argument("--flow-cap", type=int, default=0)
+    ap.add_argument("--tcp", action="store_true")
+    ap.add_argument("--closed-idle", type=float, default=None, metavar="SECONDS")
     a = ap.parse_args()
     if a.chunk_packets < 0 or a.top < 0:
         raise SystemExit("--chunk-packets / --top: want a positive count")
@@ -189,6 +225,10 @@ def main():
         raise SystemExit("--idle / --flow-cap: only with --track")
     if a.idle is not None and (a.idle < 0 or a.top):
         raise SystemExit("--idle: want a time in seconds >= 0, and no --top (flows are printed as they age out)")
+    if a.tcp and not a.track:
+        raise SystemExit("--tcp: only with --track")
+    if a.closed_idle is not None and (not a.tcp or a.idle is None or a.closed_idle < 0):
+        raise SystemExit("--closed-idle: want a time in seconds >= 0, with --tcp and --idle")
     if a.flow_cap < 0:
         raise SystemExit("--flow-cap: want a positive count")
     filters = [parse_filter(f) for f in a.filter]
@@ -219,7 +259,7 @@ def main():
     finally:
         ctx.close()
     rows = [describe(k[0], k[1], v) for k, v in table.items()] if tracked is None else tracked   # insertion order: by first packet
-    columns = COLUMNS + (("first_ts", "last_ts") if a.idle is not None else ())
+    columns = COLUMNS + (("first_ts", "last_ts") if a.idle is not None else ()) + (TCP_COLUMNS if a.tcp else ())
     if a.top:
         rows = sorted(rows, key=lambda r: (-(r["bytes"] + r["bytes_rev"]), r["first"]))[:a.top]
     if a.format == "csv":
