@@ -434,6 +434,12 @@ class HostFlowTracker:
         state's flags, into tcp_table(). Returns the result dict."""
         return flow_tcp_update_host(data, desc, flow_id, self.header()["flags"], self.tcp_table(), nbytes)
 
+    def top(self, metric: int, k: int) -> tuple:
+        """bt_flow_track_top_host: the k largest flows by a FLOW_TOP_* metric, with the side table once
+        tcp_table() has made it (the TCP metrics need it). Returns (ids, values, records, side records
+        or None, result dict)."""
+        return flow_track_top_host(self.state, metric, k, getattr(self, "tcp", None))
+
     def expire_tcp(self, now: int, idle: int, closed_idle: int, expired_cap: int | None = None, want_remap: bool = True) -> tuple:
         """bt_flow_track_expire_tcp_host with tcp_table(). Returns (expired records or None, their side
         records or None, remap [flow_cap] u32 or None, result dict)."""
@@ -504,6 +510,54 @@ def flow_track_expire_tcp_scratch_bytes(flow_cap: int) -> int:
     b = ctypes.c_uint64(0)
     _check(lib().bt_flow_track_expire_tcp_scratch_bytes(flow_cap, ctypes.byref(b)))
     return b.value
+
+
+# bt_flow_track_top_*: the metric a top-K query orders by, and its limit on k
+FLOW_TOP_BYTES, FLOW_TOP_PACKETS, FLOW_TOP_DURATION, FLOW_TOP_TCP_SYN, FLOW_TOP_TCP_RST = range(5)
+FLOW_TOP_MAX_K = 4096
+
+
+class FlowTopOpts(ctypes.Structure):
+    """bt_flow_top_opts: a FLOW_TOP_* metric and k <= FLOW_TOP_MAX_K."""
+    _fields_ = [("metric", ctypes.c_uint32), ("k", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class FlowTopResult(_Counts):
+    """bt_flow_top_result (48 B): what a top-K query found."""
+    _fields_ = [("n_flows", ctypes.c_uint32), ("n_top", ctypes.c_uint32), ("status", ctypes.c_uint32), ("metric", ctypes.c_uint32),
+                ("n_ties", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("threshold", ctypes.c_uint64),
+                ("total", ctypes.c_uint64), ("top_total", ctypes.c_uint64)]
+
+
+class FlowTopOut(ctypes.Structure):
+    """bt_flow_top_out: k entries each, all optional but result."""
+    _fields_ = [("top_id", ctypes.c_void_p), ("top_value", ctypes.c_void_p), ("top", ctypes.c_void_p), ("top_tcp", ctypes.c_void_p),
+                ("result", ctypes.c_void_p)]
+
+
+def flow_track_top_scratch_bytes(flow_cap: int, k: int) -> int:
+    """bt_flow_track_top_scratch_bytes (host only): the scratch a top-k query over a tracker of flow_cap flows needs."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_track_top_scratch_bytes(flow_cap, k, ctypes.byref(b)))
+    return b.value
+
+
+def flow_track_top_host(state: np.ndarray, metric: int, k: int, tcp: np.ndarray | None = None, want_tcp: bool | None = None) -> tuple:
+    """bt_flow_track_top_host (host only) over a tracker state's bytes (256-byte aligned) and, optionally,
+    its side table. Returns (ids [n_top] u32, values [n_top] u64, records [n_top] FlowTrackRec, side
+    records [n_top] FlowTcpRec or None, result dict)."""
+    n = max(1, k)
+    ids, vals, recs = np.zeros(n, np.uint32), np.zeros(n, np.uint64), np.zeros(n, FlowTrackRec)
+    side = np.zeros(n, FlowTcpRec) if (tcp is not None if want_tcp is None else want_tcp) else None
+    res = FlowTopResult()
+    opts = FlowTopOpts(metric, k, (ctypes.c_uint32 * 2)(0, 0))
+    out = FlowTopOut(ids.ctypes.data, vals.ctypes.data, recs.ctypes.data, side.ctypes.data if side is not None else None,
+                     ctypes.addressof(res))
+    _check(lib().bt_flow_track_top_host(state.ctypes.data, state.nbytes, ctypes.byref(opts), tcp.ctypes.data if tcp is not None else None,
+                                        ctypes.byref(out)))
+    r = res.as_dict()
+    nt = r["n_top"]
+    return ids[:nt], vals[:nt], recs[:nt], (None if side is None else side[:nt]), r
 
 
 class PcapInfo(ctypes.Structure):
@@ -624,6 +678,8 @@ EXPORTS = [
     "bt_time_flow_track", "bt_time_flow_track_host",
     "bt_flow_tcp_update_device", "bt_flow_tcp_update_host", "bt_flow_tcp_state", "bt_time_flow_tcp",
     "bt_flow_track_expire_tcp_scratch_bytes", "bt_flow_track_expire_tcp_device", "bt_flow_track_expire_tcp_host",
+    "bt_flow_track_top_scratch_bytes", "bt_flow_track_top_device", "bt_flow_track_top_host", "bt_time_flow_top",
+    "bt_time_flow_top_host",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -702,6 +758,11 @@ def lib() -> ctypes.CDLL:
                                                            ctypes.POINTER(FlowTrackExpireOut), vp]),
         "bt_flow_track_expire_tcp_host": (ctypes.c_int, [vp, u64, u64, u64, ctypes.POINTER(FlowTrackExpireTcp),
                                                          ctypes.POINTER(FlowTrackExpireOut)]),
+        "bt_flow_track_top_scratch_bytes": (ctypes.c_int, [u32, u32, ctypes.POINTER(u64)]),
+        "bt_flow_track_top_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(FlowTopOpts), vp, vp, u64, ctypes.POINTER(FlowTopOut), vp]),
+        "bt_flow_track_top_host": (ctypes.c_int, [vp, u64, ctypes.POINTER(FlowTopOpts), vp, ctypes.POINTER(FlowTopOut)]),
+        "bt_time_flow_top": (ctypes.c_int, [vp, vp, ctypes.POINTER(FlowTopOpts), vp, vp, u64, ctypes.POINTER(FlowTopOut), u32, vp]),
+        "bt_time_flow_top_host": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp, ctypes.POINTER(u64)]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -1119,6 +1180,21 @@ class Context:
         ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
         _check(lib().bt_flow_tcp_update_device(self.h, ctypes.byref(batch), ptr(flow_id), table_flags, ptr(tcp), flow_cap,
                                                ptr(result), stream))
+
+    def flow_track_top(self, state, metric: int, k: int, scratch, scratch_bytes: int, result, top_id=None, top_value=None,
+                       top=None, tcp=None, top_tcp=None, stream=None):
+        """bt_flow_track_top_device: the k (<= FLOW_TOP_MAX_K) largest flows of the tracker at `state` by
+        a FLOW_TOP_* metric, in the order (value descending, flow number ascending), into top_id (u32),
+        top_value (u64), top (FlowTrackRec) and top_tcp (FlowTcpRec; needs tcp, the side table of
+        flow_cap records, as the TCP metrics do), k entries each and all optional; nothing is written
+        at or past n_top. result: 48 B (FlowTopResult), 8-byte aligned. scratch:
+        flow_track_top_scratch_bytes(flow_cap, k) bytes, 256-byte aligned. The state and tcp are only
+        read. Pointers are addresses or DeviceBuffers. Asynchronous on `stream`."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x   # noqa: E731
+        opts = FlowTopOpts(metric, k, (ctypes.c_uint32 * 2)(0, 0))
+        out = FlowTopOut(ptr(top_id), ptr(top_value), ptr(top), ptr(top_tcp), ptr(result))
+        _check(lib().bt_flow_track_top_device(self.h, ptr(state), ctypes.byref(opts), ptr(tcp), ptr(scratch), scratch_bytes,
+                                              ctypes.byref(out), stream))
 
     def flow_track_expire_tcp(self, state, now: int, idle: int, closed_idle: int, tcp, scratch, scratch_bytes: int, result,
                               expired=None, expired_cap: int = 0, expired_tcp=None, remap=None, stream=None):

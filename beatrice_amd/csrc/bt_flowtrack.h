@@ -490,4 +490,7 @@ int launch_flowtrack(const FlowtrackArgs& a, void* stream, void* timing_stop = n
 int launch_flowexpire(const FlowexpArgs& a, void* stream);
 int launch_flowexpire_tcp(const FlowexpTcpArgs& a, void* stream);
 
+// The state `state` as bt_flow_track_init_device left it in this process (bt_flowtrack_host.cpp): false = unknown.
+bool fk_known_state(const void* state, FkShadow* sh);
+
 }  // namespace bt

@@ -235,6 +235,64 @@ int bt_time_flow_tcp(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id,
     return BT_OK;
 }
 
+int bt_time_flow_top(bt_ctx* c, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
+                     uint64_t scratch_bytes, const bt_flow_top_out* out, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !iters || !ms) return set_error(BT_E_INVALID_ARGUMENT, "null argument / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int rc = run_flow_track_top(c, state, opts, tcp, scratch, scratch_bytes, out, c->stream, c->timing.tev[2 * i],
+                                        c->timing.tev[2 * i + 1])) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
+// What the top-K query replaces: every record of the tracker copied to pinned host memory, then the
+// k largest by bytes picked on the calling thread (tools/pcap_flows.py's download and sorted()[:k], in C++).
+int bt_time_flow_top_host(bt_ctx* c, const bt_flow_track_rec* recs, uint32_t n_flows, uint32_t k, uint32_t iters, float* copy_ms,
+                          float* sort_ms, uint64_t* top_total) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !recs || !n_flows || !iters || !copy_ms || !sort_ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / no flows / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    bt_flow_track_rec* h = nullptr;
+    HIP_TRY(hipHostMalloc(&h, (size_t)n_flows * sizeof(bt_flow_track_rec), hipHostMallocDefault));
+    std::memset(static_cast<void*>(h), 0, (size_t)n_flows * sizeof(bt_flow_track_rec));   // first touch outside the timed part
+    std::vector<uint32_t> order(n_flows);
+    const uint32_t top = k < n_flows ? k : n_flows;
+    const auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto ms = [](auto a, auto b) { return std::chrono::duration<float, std::milli>(b - a).count(); };
+    hipError_t err = hipSuccess;
+    uint64_t sum = 0;
+    for (uint32_t it = 0; it < iters && err == hipSuccess; ++it) {
+        const auto t0 = now();
+        err = hipMemcpyAsync(h, recs, (size_t)n_flows * sizeof(bt_flow_track_rec), hipMemcpyDeviceToHost, c->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+        const auto t1 = now();
+        if (err == hipSuccess) {
+            for (uint32_t f = 0; f < n_flows; ++f) order[f] = f;
+            const auto val = [&](uint32_t f) { return h[f].bytes[0] + h[f].bytes[1]; };
+            std::partial_sort(order.begin(), order.begin() + top, order.end(),
+                              [&](uint32_t x, uint32_t y) { return val(x) != val(y) ? val(x) > val(y) : x < y; });
+            sum = 0;
+            for (uint32_t r = 0; r < top; ++r) sum += val(order[r]);
+        }
+        copy_ms[it] = ms(t0, t1);
+        sort_ms[it] = ms(t1, now());
+    }
+    if (top_total) *top_total = sum;   // so that the result is used (and can be checked)
+    (void)hipHostFree(h);
+    if (err != hipSuccess) return set_error(BT_E_INTERNAL, "bt_time_flow_top_host: %s", hipGetErrorString(err));
+    return BT_OK;
+}
+
 // What the tracker replaces: a batch's flow records copied to pinned host memory, then merged into
 // a table on the calling thread (tools/pcap_flows.py's per-chunk download and fold, in C++).
 int bt_time_flow_track_host(bt_ctx* c, const bt_flow_rec* flows, uint32_t n_flows, void* host_state, uint64_t state_bytes,

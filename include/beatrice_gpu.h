@@ -88,7 +88,8 @@ extern "C" {
  * bt_flow_track_update_host, bt_flow_track_expire_host, bt_flow_track_forget,
  * bt_flow_tcp_update_device, bt_flow_tcp_update_host, bt_flow_tcp_state,
  * bt_flow_track_expire_tcp_scratch_bytes, bt_flow_track_expire_tcp_device,
- * bt_flow_track_expire_tcp_host. */
+ * bt_flow_track_expire_tcp_host, bt_flow_track_top_scratch_bytes, bt_flow_track_top_device,
+ * bt_flow_track_top_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -858,6 +859,69 @@ int  bt_flow_track_expire_tcp_device(bt_ctx* ctx, void* state, uint64_t now, uin
                                      void* scratch, uint64_t scratch_bytes, const bt_flow_track_expire_out* out, void* stream);
 int  bt_flow_track_expire_tcp_host(void* state, uint64_t state_bytes, uint64_t now, uint64_t idle,
                                    const bt_flow_track_expire_tcp* x, const bt_flow_track_expire_out* out);
+
+/* ---- top-K flows of a tracker: the largest flows by a measure, selected on the device ------
+ * bt_flow_track_top_device: the k largest flows of the tracker at `state` by opts->metric,
+ * selected, ordered and gathered on the device; only k records need leave it.
+ * Value: the value of flow f (0 <= f < n_flows) is a u64 computed from its record,
+ *   BT_FLOW_TOP_BYTES bytes[0] + bytes[1], BT_FLOW_TOP_PACKETS packets[0] + packets[1] (both mod
+ *   2^64), BT_FLOW_TOP_DURATION last_ts >= first_ts ? last_ts - first_ts : 0, BT_FLOW_TOP_TCP_SYN
+ *   tcp[f].syn_packets, BT_FLOW_TOP_TCP_RST tcp[f].rst_packets (`tcp`: the tracker's side table,
+ *   flow_cap records). total and top_total are sums of values mod 2^64.
+ * Order: value descending, then flow number ascending. The top is the first n_top = min(k,
+ *   n_flows) flows in that order, and entry r of every output array belongs to rank r. A
+ *   zero-valued flow ranks like any other. Ties at the threshold (the value of the last flow of
+ *   the top) therefore go to the lowest flow numbers, the earliest-seen flows. n_ties counts the
+ *   flows of the whole table whose value equals the threshold; with n_top == 0 threshold and
+ *   n_ties are 0.
+ * Bounds: nothing is written at or past n_top in any output array; nothing in the state or in
+ *   `tcp` is written at all. k == 0 is legal: *result has n_top = 0, n_flows and total.
+ * As the tracker's calls: asynchronous on `stream` (NULL = the context's), no allocation, no host
+ *   synchronisation and no device-to-host read; the caller orders it on the state's stream behind
+ *   the update (and the bt_flow_tcp_update_device) it wants to see. The state's geometry comes
+ *   from what the process remembers of it; the kernels compare it with the header and on a
+ *   mismatch write status = 1, every other field of *result 0 and nothing else. The host never
+ *   knows n_flows: grids are sized by flow_cap and threads at or past n_flows do nothing. Scratch:
+ *   bt_flow_track_top_scratch_bytes(flow_cap, k) bytes of the caller's device memory, 256-byte
+ *   aligned (one u64 per flow, the histograms, per-block partials, k candidates). Exact and
+ *   bit-identical from run to run: integer sums and ordered scans only.
+ * bt_flow_track_top_host: the same on the calling thread over a state in host memory (tcp, the
+ *   outputs and *result in host memory), bit-identical.
+ * BT_E_INVALID_ARGUMENT, decided before the context or any HIP call: a null state, opts, out,
+ *   result or scratch; misalignment (state and scratch 256 bytes; result, top_value and top 8;
+ *   top_id, tcp and top_tcp 4); k > BT_FLOW_TOP_MAX_K; an unknown metric or non-zero reserved
+ *   fields; a TCP metric or top_tcp with tcp == NULL; a state the process does not know (host
+ *   form: the header checks of the tracker's host forms); scratch_bytes below the need (which the
+ *   state's flow_cap decides); then a null context. */
+#define BT_FLOW_TOP_MAX_K 4096u
+enum { BT_FLOW_TOP_BYTES = 0,      /* bytes[0] + bytes[1]                        */
+       BT_FLOW_TOP_PACKETS = 1,    /* packets[0] + packets[1]                    */
+       BT_FLOW_TOP_DURATION = 2,   /* last_ts >= first_ts ? last_ts - first_ts : 0 */
+       BT_FLOW_TOP_TCP_SYN = 3,    /* tcp[f].syn_packets  (needs the side table) */
+       BT_FLOW_TOP_TCP_RST = 4 };  /* tcp[f].rst_packets  (needs the side table) */
+
+typedef struct bt_flow_top_opts { uint32_t metric, k, reserved[2]; } bt_flow_top_opts;     /* reserved = 0 */
+typedef struct bt_flow_top_result {   /* 48 B, device-visible, 8-byte aligned */
+    uint32_t n_flows, n_top;          /* n_top = min(k, n_flows) */
+    uint32_t status, metric;          /* status as the tracker's: 1 = not this tracker's state, nothing done */
+    uint32_t n_ties, reserved;        /* flows of the whole table whose value == threshold */
+    uint64_t threshold;               /* value of the last flow of the top, 0 when n_top == 0 */
+    uint64_t total, top_total;        /* sum of the value over all flows / over the top, mod 2^64 */
+} bt_flow_top_result;
+typedef struct bt_flow_top_out {
+    uint32_t*          top_id;     /* optional, k entries: flow numbers                  */
+    uint64_t*          top_value;  /* optional, k entries                                */
+    bt_flow_track_rec* top;        /* optional, k records                                */
+    bt_flow_tcp_rec*   top_tcp;    /* optional, k records; needs `tcp`                   */
+    bt_flow_top_result* result;    /* required                                           */
+} bt_flow_top_out;
+
+int  bt_flow_track_top_scratch_bytes(uint32_t flow_cap, uint32_t k, uint64_t* bytes);   /* host only */
+int  bt_flow_track_top_device(bt_ctx* ctx, const void* state, const bt_flow_top_opts* opts,
+                              const bt_flow_tcp_rec* tcp /* optional, flow_cap */, void* scratch, uint64_t scratch_bytes,
+                              const bt_flow_top_out* out, void* stream);
+int  bt_flow_track_top_host(const void* state, uint64_t state_bytes, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp,
+                            const bt_flow_top_out* out);
 
 /* ---- pcap capture files ------------------------------------------------------------
  * Classic pcap (24-B global header, 16-B record headers), link type 1 (Ethernet), in all four

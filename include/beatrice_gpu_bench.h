@@ -131,6 +131,16 @@ int  bt_time_flow_tcp(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_
 int  bt_time_flow_track_host(bt_ctx* ctx, const bt_flow_rec* flows, uint32_t n_flows, void* host_state,
                              uint64_t state_bytes, uint64_t batch_ts, uint32_t iters, float* copy_ms, float* merge_ms,
                              bt_flow_track_result* last);
+/* bt_flow_track_top_device `iters` times on the context's stream over the same state; ms[i] = call
+ * i's kernels, from an event pair recorded by the first and the last kernel's own dispatches. */
+int  bt_time_flow_top(bt_ctx* ctx, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp,
+                      void* scratch, uint64_t scratch_bytes, const bt_flow_top_out* out, uint32_t iters, float* ms);
+/* What the top-K query replaces, `iters` times: copy_ms[i] = the n_flows records of a tracker
+ * (recs, on the device) copied to pinned host memory (wall clock, the wait included), sort_ms[i] =
+ * a std::partial_sort of them by (bytes descending, flow number ascending) for the first k on the
+ * calling thread. top_total (optional): the sum of the last top's values. */
+int  bt_time_flow_top_host(bt_ctx* ctx, const bt_flow_track_rec* recs, uint32_t n_flows, uint32_t k, uint32_t iters,
+                           float* copy_ms, float* sort_ms, uint64_t* top_total);
 /* A device-to-device hipMemcpyAsync of `bytes` on the context's stream, `iters` times, each
  * between an event pair: the ceiling for moving that many bytes on the device. */
 int  bt_time_copy_d2d(bt_ctx* ctx, void* dst, const void* src, uint64_t bytes, uint32_t iters, float* ms);

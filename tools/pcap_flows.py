@@ -4,7 +4,8 @@ the file (the NetFlow / conntrack view of a capture).
 
 Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [--bidirectional] [--l3-only]
                                   [--top N] [--format csv|json] [--chunk-packets N]
-                                  [--track [--idle SECONDS] [--flow-cap N] [--tcp [--closed-idle SECONDS]]]
+                                  [--track [--idle SECONDS] [--flow-cap N] [--tcp [--closed-idle SECONDS]]
+                                           [--by bytes|packets|duration|syn|rst]]
   --filter         as tools/pcap_filter.py takes it; only passing packets are counted
   --bidirectional  both directions of a conversation are one flow (BT_FLOWTAB_BIDIRECTIONAL): the
                    listed source is the smaller endpoint, packets_rev / bytes_rev count the other direction
@@ -27,6 +28,13 @@ Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [-
                    (packets with SYN and no ACK, with FIN, with RST). Still one wait without --idle.
   --closed-idle SECONDS  with --tcp and --idle: a closed or reset connection ages out once its last packet is more
                    than SECONDS older than the chunk's last packet (bt_flow_track_expire_tcp_device)
+  --by MEASURE     with --track and --top N, N <= 4096: what the top is ordered by, largest first and the
+                   earliest-seen flow first among equals: bytes (default), packets (both directions), duration
+                   (last minus first packet time by the pcap record headers), syn or rst (with --tcp: packets with
+                   SYN and no ACK, with RST)
+With --track and --top N, N <= 4096, the top is selected on the device (bt_flow_track_top_device behind the
+last update): still one wait, then only the N records (and N side records with --tcp) are read. A larger N
+downloads every record and sorts here, as the default path does.
 The file is taken in chunks of whole records, as tools/pcap_stats.py takes it. Per chunk: with
 filters the filter-only bt_parse_filter_device, then bt_flow_table_device over its verdict words
 (without filters over every packet). Only the 72-byte result and flows[0 .. n_written) come back
@@ -55,6 +63,8 @@ K_HOST = 9   # enum bt_filter_kind
 COLUMNS = ("class", "src", "dst", "sport", "dport", "packets", "bytes", "packets_rev", "bytes_rev", "first", "last")
 TCP_COLUMNS = ("tcp_flags_fwd", "tcp_flags_rev", "tcp_state", "syn", "fin", "rst")
 U64_MAX = (1 << 64) - 1
+TOP_BY = {"bytes": abi.FLOW_TOP_BYTES, "packets": abi.FLOW_TOP_PACKETS, "duration": abi.FLOW_TOP_DURATION,
+          "syn": abi.FLOW_TOP_TCP_SYN, "rst": abi.FLOW_TOP_TCP_RST}
 
 
 def describe(klass: int, key: bytes, v: list) -> dict:
@@ -92,7 +102,9 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
     unit = 1_000_000_000 if info["nanosecond"] else 1_000_000
     starts = np.array([lo for lo, _ in parts] + [0], np.int64)
     timed = a.idle is not None
-    if timed:   # a record's header is the 16 bytes before its data: ts_sec, ts_frac in the file's byte order
+    on_device = 0 < a.top <= abi.FLOW_TOP_MAX_K   # the top comes from the device (--idle with --top is refused)
+    stamped = timed or (on_device and a.by == "duration")
+    if stamped:   # a record's header is the 16 bytes before its data: ts_sec, ts_frac in the file's byte order
         head = np.stack([data[off - 16 + k] for k in range(8)], axis=1).astype(np.uint64) if len(off) else np.zeros((0, 8), np.uint64)
         order = (3, 2, 1, 0) if info["swapped"] else (0, 1, 2, 3)
         word = lambda b: sum(head[:, b + order[k]] << np.uint64(8 * k) for k in range(4))  # noqa: E731
@@ -132,6 +144,13 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
             d_exp_tcp = ctx.alloc(16 * cap)
             bufs.append(d_exp_tcp)
         closed = U64_MAX if a.closed_idle is None else int(a.closed_idle * unit)
+    if stamped and not timed:
+        d_ts = ctx.alloc(max(16, max_n * 8))
+        bufs.append(d_ts)
+    if on_device:
+        tneed = abi.flow_track_top_scratch_bytes(cap, a.top)
+        d_tscratch, d_top, d_top_tcp, d_top_res = ctx.alloc(tneed), ctx.alloc(104 * a.top), ctx.alloc(16 * a.top), ctx.alloc(48)
+        bufs += [d_tscratch, d_top, d_top_tcp, d_top_res]
     ctx.reserve(max_n)
     ctx.flow_track_init(d_state, lay["total"], cap, flags)
     for lo, hi in parts:
@@ -139,13 +158,13 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         nbytes = int(off[hi - 1] + ln[hi - 1]) - first
         d_data.upload(data[first:first + nbytes])   # waits for the context's stream: the last chunk is done
         d_desc.upload((off[lo:hi] - first).astype(np.uint64) | (ln[lo:hi].astype(np.uint64) << np.uint64(48)))
-        if timed:
+        if stamped:
             d_ts.upload(ts[lo:hi])
         batch = abi.Batch(d_data.ptr, d_desc.ptr, 0, n, max(nbytes, 1), abi.DESC_PACKED, 0)
         if filters:
             ctx.run_device(batch, abi.Outputs(None, 0, d_ver.ptr, None, None, None))
         ctx.flow_track_update(d_state, batch, d_scratch, need, d_res, select=d_ver if filters else None,
-                              ts=d_ts if timed else None, flow_id=d_ids if a.tcp else None)
+                              ts=d_ts if stamped else None, flow_id=d_ids if a.tcp else None)
         if a.tcp:
             ctx.flow_tcp_update(batch, d_ids, flags, d_tcp, cap, d_tres)
         if timed:   # what aged out is printed now: its count and records come back, nothing else
@@ -159,11 +178,22 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
             if x["n_expired"]:
                 lines(d_exp.download(np.zeros(104 * x["n_expired"], np.uint8)).view(abi.FlowTrackRec),
                       d_exp_tcp.download(np.zeros(16 * x["n_expired"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None)
+    if on_device:   # behind the last update and side table update, on their stream
+        ctx.flow_track_top(d_state, TOP_BY[a.by], a.top, d_tscratch, tneed, d_top_res, top=d_top, tcp=d_tcp if a.tcp else None,
+                           top_tcp=d_top_tcp if a.tcp else None)
     ctx.synchronize()   # the one wait of the plain --track path
     hdr = abi.FlowTrackHdr.from_bytes(d_state.download(np.zeros(128, np.uint8))).as_dict()
     if hdr["overflow_packets"]:
         raise SystemExit(f"pcap_flows: more than --flow-cap {cap} flows at once")
-    if hdr["n_flows"]:
+    if on_device:
+        totals["flows"] = hdr["n_flows"]   # not the lines printed
+        res = abi.FlowTopResult.from_bytes(d_top_res.download(np.zeros(48, np.uint8))).as_dict()
+        if res["status"] or res["n_flows"] != hdr["n_flows"]:
+            raise SystemExit("pcap_flows: the top-K query did not see the tracker")
+        if res["n_top"]:   # only the top's records cross PCIe
+            lines(d_top.download(np.zeros(104 * res["n_top"], np.uint8)).view(abi.FlowTrackRec),
+                  d_top_tcp.download(np.zeros(16 * res["n_top"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None)
+    elif hdr["n_flows"]:
         both = d_state.download(np.zeros(lay["records"] + 104 * hdr["n_flows"], np.uint8))
         lines(both[lay["records"]:].view(abi.FlowTrackRec),
               d_tcp.download(np.zeros(16 * hdr["n_flows"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None)
@@ -218,6 +248,7 @@ def main():
     ap.add_argument("--flow-cap", type=int, default=0)
     ap.add_argument("--tcp", action="store_true")
     ap.add_argument("--closed-idle", type=float, default=None, metavar="SECONDS")
+    ap.add_argument("--by", choices=tuple(TOP_BY), default=None)
     a = ap.parse_args()
     if a.chunk_packets < 0 or a.top < 0:
         raise SystemExit("--chunk-packets / --top: want a positive count")
@@ -231,6 +262,11 @@ def main():
         raise SystemExit("--closed-idle: want a time in seconds >= 0, with --tcp and --idle")
     if a.flow_cap < 0:
         raise SystemExit("--flow-cap: want a positive count")
+    if a.by is not None and not (a.track and 0 < a.top <= abi.FLOW_TOP_MAX_K):
+        raise SystemExit(f"--by: only with --track and --top N, N <= {abi.FLOW_TOP_MAX_K}")
+    if a.by in ("syn", "rst") and not a.tcp:
+        raise SystemExit("--by syn / rst: only with --tcp")
+    a.by = a.by or "bytes"
     filters = [parse_filter(f) for f in a.filter]
     data = np.fromfile(a.src, np.uint8)
     try:
@@ -260,7 +296,7 @@ def main():
         ctx.close()
     rows = [describe(k[0], k[1], v) for k, v in table.items()] if tracked is None else tracked   # insertion order: by first packet
     columns = COLUMNS + (("first_ts", "last_ts") if a.idle is not None else ()) + (TCP_COLUMNS if a.tcp else ())
-    if a.top:
+    if a.top and not (a.track and a.top <= abi.FLOW_TOP_MAX_K):   # otherwise the device selected and ordered them
         rows = sorted(rows, key=lambda r: (-(r["bytes"] + r["bytes_rev"]), r["first"]))[:a.top]
     if a.format == "csv":
         print(",".join(columns))
@@ -269,7 +305,7 @@ def main():
     else:
         for r in rows:
             print(json.dumps(r))
-    totals["flows"] = len(table) if tracked is None else len(tracked)
+    totals["flows"] = len(table) if tracked is None else totals.get("flows", len(tracked))
     print(json.dumps(totals), file=sys.stderr)
 
 
