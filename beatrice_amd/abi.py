@@ -440,6 +440,12 @@ class HostFlowTracker:
         or None, result dict)."""
         return flow_track_top_host(self.state, metric, k, getattr(self, "tcp", None))
 
+    def hosts(self, host_cap: int | None = None, slots: int = 0, want_endpoints: bool = True) -> tuple:
+        """bt_flow_track_hosts_host: the tracker's flows aggregated per address, with the side table once
+        tcp_table() has made it. Returns (host records [n_written] FlowHostRec, endpoint_host
+        [2 n_flows] u32 or None, result dict)."""
+        return flow_track_hosts_host(self.state, host_cap, slots, getattr(self, "tcp", None), want_endpoints)
+
     def expire_tcp(self, now: int, idle: int, closed_idle: int, expired_cap: int | None = None, want_remap: bool = True) -> tuple:
         """bt_flow_track_expire_tcp_host with tcp_table(). Returns (expired records or None, their side
         records or None, remap [flow_cap] u32 or None, result dict)."""
@@ -558,6 +564,59 @@ def flow_track_top_host(state: np.ndarray, metric: int, k: int, tcp: np.ndarray 
     r = res.as_dict()
     nt = r["n_top"]
     return ids[:nt], vals[:nt], recs[:nt], (None if side is None else side[:nt]), r
+
+
+FlowHostRec = np.dtype({
+    "names": ["addr", "family", "pad", "first_flow", "flows", "packets", "bytes", "first_ts", "last_ts", "tcp_state", "syn_flows",
+              "syn_packets", "fin_packets", "rst_packets"],
+    "formats": [("u1", 16), "u1", ("u1", 3), "<u4", ("<u4", 2), ("<u8", 2), ("<u8", 2), "<u8", "<u8", ("<u4", 7), ("<u4", 2),
+                "<u4", "<u4", "<u4"],
+    "offsets": [0, 16, 17, 20, 24, 32, 48, 64, 72, 80, 108, 116, 120, 124],
+    "itemsize": 128,
+})
+
+
+class FlowHostsOpts(ctypes.Structure):
+    """bt_flow_hosts_opts: the endpoint table's slots (0 = auto, 4 flow_cap) and how many host records to write."""
+    _fields_ = [("slots", ctypes.c_uint32), ("host_cap", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class FlowHostsResult(_Counts):
+    """bt_flow_hosts_result (64 B): what an endpoint-table query found."""
+    _fields_ = [("n_flows", ctypes.c_uint32), ("n_hosts", ctypes.c_uint32), ("n_written", ctypes.c_uint32), ("status", ctypes.c_uint32),
+                ("overflow_endpoints", ctypes.c_uint32), ("slots", ctypes.c_uint32), ("hosts_v4", ctypes.c_uint32),
+                ("hosts_v6", ctypes.c_uint32), ("packets_total", ctypes.c_uint64), ("bytes_total", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64 * 2)]
+
+
+class FlowHostsOut(ctypes.Structure):
+    """bt_flow_hosts_out: host_cap records, 2 flow_cap host numbers (optional), the result (required)."""
+    _fields_ = [("hosts", ctypes.c_void_p), ("endpoint_host", ctypes.c_void_p), ("result", ctypes.c_void_p)]
+
+
+def flow_track_hosts_scratch_bytes(flow_cap: int, slots: int = 0) -> int:
+    """bt_flow_track_hosts_scratch_bytes (host only): the scratch an endpoint-table query over a tracker of flow_cap flows needs."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_track_hosts_scratch_bytes(flow_cap, slots, ctypes.byref(b)))
+    return b.value
+
+
+def flow_track_hosts_host(state: np.ndarray, host_cap: int | None = None, slots: int = 0, tcp: np.ndarray | None = None,
+                          want_endpoints: bool = True) -> tuple:
+    """bt_flow_track_hosts_host (host only) over a tracker state's bytes (256-byte aligned) and, optionally,
+    its side table. host_cap None = room for every host. Returns (host records [n_written] FlowHostRec,
+    endpoint_host [2 n_flows] u32 or None, result dict)."""
+    hdr = FlowTrackHdr.from_bytes(state[:128]).as_dict()
+    cap = 2 * hdr["flow_cap"] if host_cap is None else host_cap
+    hosts = np.zeros(max(1, cap), FlowHostRec)
+    ends = np.zeros(max(1, 2 * hdr["flow_cap"]), np.uint32) if want_endpoints else None
+    res = FlowHostsResult()
+    opts = FlowHostsOpts(slots, cap, (ctypes.c_uint32 * 2)(0, 0))
+    out = FlowHostsOut(hosts.ctypes.data, ends.ctypes.data if ends is not None else None, ctypes.addressof(res))
+    _check(lib().bt_flow_track_hosts_host(state.ctypes.data, state.nbytes, ctypes.byref(opts), tcp.ctypes.data if tcp is not None else None,
+                                          ctypes.byref(out)))
+    r = res.as_dict()
+    return hosts[:r["n_written"]], (None if ends is None else ends[:2 * r["n_flows"]]), r
 
 
 class PcapInfo(ctypes.Structure):
@@ -680,6 +739,8 @@ EXPORTS = [
     "bt_flow_track_expire_tcp_scratch_bytes", "bt_flow_track_expire_tcp_device", "bt_flow_track_expire_tcp_host",
     "bt_flow_track_top_scratch_bytes", "bt_flow_track_top_device", "bt_flow_track_top_host", "bt_time_flow_top",
     "bt_time_flow_top_host",
+    "bt_flow_track_hosts_scratch_bytes", "bt_flow_track_hosts_device", "bt_flow_track_hosts_host", "bt_time_flow_hosts",
+    "bt_time_flow_hosts_host",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -763,6 +824,11 @@ def lib() -> ctypes.CDLL:
         "bt_flow_track_top_host": (ctypes.c_int, [vp, u64, ctypes.POINTER(FlowTopOpts), vp, ctypes.POINTER(FlowTopOut)]),
         "bt_time_flow_top": (ctypes.c_int, [vp, vp, ctypes.POINTER(FlowTopOpts), vp, vp, u64, ctypes.POINTER(FlowTopOut), u32, vp]),
         "bt_time_flow_top_host": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp, ctypes.POINTER(u64)]),
+        "bt_flow_track_hosts_scratch_bytes": (ctypes.c_int, [u32, u32, ctypes.POINTER(u64)]),
+        "bt_flow_track_hosts_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(FlowHostsOpts), vp, vp, u64, ctypes.POINTER(FlowHostsOut), vp]),
+        "bt_flow_track_hosts_host": (ctypes.c_int, [vp, u64, ctypes.POINTER(FlowHostsOpts), vp, ctypes.POINTER(FlowHostsOut)]),
+        "bt_time_flow_hosts": (ctypes.c_int, [vp, vp, ctypes.POINTER(FlowHostsOpts), vp, vp, u64, ctypes.POINTER(FlowHostsOut), u32, vp]),
+        "bt_time_flow_hosts_host": (ctypes.c_int, [vp, vp, u32, vp, ctypes.POINTER(FlowHostsOpts), u32, vp, vp, vp, vp]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -1195,6 +1261,21 @@ class Context:
         out = FlowTopOut(ptr(top_id), ptr(top_value), ptr(top), ptr(top_tcp), ptr(result))
         _check(lib().bt_flow_track_top_device(self.h, ptr(state), ctypes.byref(opts), ptr(tcp), ptr(scratch), scratch_bytes,
                                               ctypes.byref(out), stream))
+
+    def flow_track_hosts(self, state, host_cap: int, scratch, scratch_bytes: int, result, hosts=None, endpoint_host=None,
+                         tcp=None, slots: int = 0, stream=None):
+        """bt_flow_track_hosts_device: the flows of the tracker at `state` aggregated per address into
+        hosts (host_cap FlowHostRec, numbered in order of first appearance; optional with host_cap 0)
+        and endpoint_host (2 flow_cap u32, optional: the host number of every flow's two endpoints);
+        with tcp (the side table of flow_cap records) the state counts and SYN columns too. result:
+        64 B (FlowHostsResult), 8-byte aligned. scratch: flow_track_hosts_scratch_bytes(flow_cap,
+        slots) bytes, 256-byte aligned. The state and tcp are only read. Pointers are addresses or
+        DeviceBuffers. Asynchronous on `stream`."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x   # noqa: E731
+        opts = FlowHostsOpts(slots, host_cap, (ctypes.c_uint32 * 2)(0, 0))
+        out = FlowHostsOut(ptr(hosts), ptr(endpoint_host), ptr(result))
+        _check(lib().bt_flow_track_hosts_device(self.h, ptr(state), ctypes.byref(opts), ptr(tcp), ptr(scratch), scratch_bytes,
+                                                ctypes.byref(out), stream))
 
     def flow_track_expire_tcp(self, state, now: int, idle: int, closed_idle: int, tcp, scratch, scratch_bytes: int, result,
                               expired=None, expired_cap: int = 0, expired_tcp=None, remap=None, stream=None):

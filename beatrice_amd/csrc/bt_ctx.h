@@ -257,6 +257,10 @@ int run_flow_tcp(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, uin
 int run_flow_track_top(bt_ctx* c, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
                        uint64_t scratch_bytes, const bt_flow_top_out* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 
+// bt_flowhosts_host.cpp (bt_timing.cpp's bt_time_flow_hosts times the same launches)
+int run_flow_track_hosts(bt_ctx* c, const void* state, const bt_flow_hosts_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
+                         uint64_t scratch_bytes, const bt_flow_hosts_out* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+
 // bt_extract_host.cpp (bt_timing.cpp's bt_time_extract2 times the same launch)
 int build_table(const bt_field_def* f, uint32_t n, ExTable* t, uint64_t* span_out, bool* never);
 int run_extract(bt_ctx* c, const bt_batch* b, const ExTable& t, bool never, const bt_extract_out* o, hipStream_t st,

@@ -56,7 +56,7 @@ bool forget_state(const void* state) {
 
 namespace bt {
 
-bool fk_known_state(const void* state, FkShadow* sh) { return known_state(state, sh); }   // for bt_flowtop_host.cpp
+bool fk_known_state(const void* state, FkShadow* sh) { return known_state(state, sh); }   // for bt_flowtop_host.cpp, bt_flowhosts_host.cpp
 
 // e0 / e1: timing events recorded by the first / last kernel's own dispatch (bt_time_flow_track).
 int run_flow_track_update(bt_ctx* c, void* state, const bt_batch* frames, const uint64_t* select, const bt_flow_track_update* upd,

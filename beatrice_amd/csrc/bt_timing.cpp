@@ -293,6 +293,84 @@ int bt_time_flow_top_host(bt_ctx* c, const bt_flow_track_rec* recs, uint32_t n_f
     return BT_OK;
 }
 
+int bt_time_flow_hosts(bt_ctx* c, const void* state, const bt_flow_hosts_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
+                       uint64_t scratch_bytes, const bt_flow_hosts_out* out, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !iters || !ms) return set_error(BT_E_INVALID_ARGUMENT, "null argument / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int rc = run_flow_track_hosts(c, state, opts, tcp, scratch, scratch_bytes, out, c->stream, c->timing.tev[2 * i],
+                                          c->timing.tev[2 * i + 1])) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
+// What the endpoint table replaces: the header and the n_flows records of a tracker, and its side
+// records, copied to pinned host memory, then bt_flow_track_hosts_host over them on the calling thread.
+int bt_time_flow_hosts_host(bt_ctx* c, const void* state, uint32_t n_flows, const bt_flow_tcp_rec* tcp,
+                            const bt_flow_hosts_opts* opts, uint32_t iters, float* copy_ms, float* group_ms,
+                            bt_flow_hosts_result* last, uint64_t* sums) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    bt::FkShadow sh{};
+    bt_flow_track_sizes sl{};
+    char why[128];
+    if (!c || !state || !opts || !iters || !copy_ms || !group_ms || !bt::fk_known_state(state, &sh) ||
+        !bt::fk_layout(sh.flow_cap, sh.slots, &sl, why, sizeof(why)) || n_flows > sh.flow_cap)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / unknown state / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t head = (size_t)sl.records + (size_t)n_flows * sizeof(bt_flow_track_rec), side = (size_t)n_flows * sizeof(bt_flow_tcp_rec);
+    uint8_t* h = nullptr;
+    bt_flow_tcp_rec* ht = nullptr;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h), (size_t)sl.total, hipHostMallocDefault));   // 256-byte aligned and more
+    if (tcp && hipHostMalloc(reinterpret_cast<void**>(&ht), side ? side : 16u, hipHostMallocDefault) != hipSuccess) {
+        (void)hipHostFree(h);
+        return set_error(BT_E_RESOURCE, "bt_time_flow_hosts_host: no pinned memory for the side table");
+    }
+    std::memset(h, 0, head);   // first touch outside the timed part
+    if (ht) std::memset(static_cast<void*>(ht), 0, side);
+    std::vector<bt_flow_host_rec> hosts(opts->host_cap ? opts->host_cap : 1u);
+    const auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto ms = [](auto a, auto b) { return std::chrono::duration<float, std::milli>(b - a).count(); };
+    hipError_t err = hipSuccess;
+    int rc = BT_OK;
+    bt_flow_hosts_result res{};
+    for (uint32_t it = 0; it < iters && err == hipSuccess && rc == BT_OK; ++it) {
+        const auto t0 = now();
+        err = hipMemcpyAsync(h, state, head, hipMemcpyDeviceToHost, c->stream);
+        if (err == hipSuccess && ht && side) err = hipMemcpyAsync(ht, tcp, side, hipMemcpyDeviceToHost, c->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+        const auto t1 = now();
+        if (err == hipSuccess) {
+            const bt_flow_hosts_out out{hosts.data(), nullptr, &res};
+            rc = bt_flow_track_hosts_host(h, sl.total, opts, ht, &out);
+        }
+        copy_ms[it] = ms(t0, t1);
+        group_ms[it] = ms(t1, now());
+    }
+    if (last) *last = res;   // so that the result is used (and can be checked)
+    if (sums) {   // over the records the last run wrote: what the caller compares the device's records with
+        for (int j = 0; j < 6; ++j) sums[j] = 0;
+        for (uint32_t k = 0; k < res.n_written; ++k) {
+            const bt_flow_host_rec& r = hosts[k];
+            sums[0] += r.packets[0]; sums[1] += r.packets[1]; sums[2] += r.bytes[0] ^ r.bytes[1];
+            sums[3] += (uint64_t)r.flows[0] + r.flows[1];
+            for (int j = 0; j < 7; ++j) sums[4] += (uint64_t)r.tcp_state[j] * (uint64_t)(j + 1);
+            sums[5] += r.first_ts ^ r.last_ts ^ ((uint64_t)r.first_flow << 32 | r.syn_packets);
+        }
+    }
+    (void)hipHostFree(h);
+    if (ht) (void)hipHostFree(ht);
+    if (err != hipSuccess) return set_error(BT_E_INTERNAL, "bt_time_flow_hosts_host: %s", hipGetErrorString(err));
+    return rc;
+}
+
 // What the tracker replaces: a batch's flow records copied to pinned host memory, then merged into
 // a table on the calling thread (tools/pcap_flows.py's per-chunk download and fold, in C++).
 int bt_time_flow_track_host(bt_ctx* c, const bt_flow_rec* flows, uint32_t n_flows, void* host_state, uint64_t state_bytes,

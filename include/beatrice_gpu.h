@@ -89,7 +89,8 @@ extern "C" {
  * bt_flow_tcp_update_device, bt_flow_tcp_update_host, bt_flow_tcp_state,
  * bt_flow_track_expire_tcp_scratch_bytes, bt_flow_track_expire_tcp_device,
  * bt_flow_track_expire_tcp_host, bt_flow_track_top_scratch_bytes, bt_flow_track_top_device,
- * bt_flow_track_top_host. */
+ * bt_flow_track_top_host, bt_flow_track_hosts_scratch_bytes, bt_flow_track_hosts_device,
+ * bt_flow_track_hosts_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -922,6 +923,84 @@ int  bt_flow_track_top_device(bt_ctx* ctx, const void* state, const bt_flow_top_
                               const bt_flow_top_out* out, void* stream);
 int  bt_flow_track_top_host(const void* state, uint64_t state_bytes, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp,
                             const bt_flow_top_out* out);
+
+/* ---- endpoint table of a tracker: the tracker's flows aggregated per host on the device ----
+ * bt_flow_track_hosts_device: a second exact group-by, on the address instead of the flow key,
+ * over the records of the tracker at `state` (Wireshark's "Endpoints" beside its
+ * "Conversations"): one bt_flow_host_rec per distinct address.
+ * Contributions: every live flow f < n_flows gives two, c = 2 f + role. Role 0 is the key's first
+ *   endpoint, role 1 its second; the address is key bytes 0..3 / 4..7 for BT_FLOW_V4 /
+ *   BT_FLOW_V4_L4 (family 4, the other 12 address bytes zero) and key bytes 0..15 / 16..31 for
+ *   BT_FLOW_V6 / BT_FLOW_V6_L4 (family 6). Ports are never part of a host. Two contributions are
+ *   one host when family and the 16 address bytes are equal: bytes are compared, never hashes.
+ *   IPv4 1.2.3.4 and IPv6 0102:0304:: are different hosts.
+ * Sums: a role-r contribution of flow f adds the record's packets[r] / bytes[r] to the host's
+ *   packets[0] / bytes[0] (sent) and packets[1-r] / bytes[1-r] to its [1] (received), 1 to
+ *   flows[r], takes the minimum of first_ts, the maximum of last_ts and the minimum of f into
+ *   first_flow. That is right for bidirectional trackers and for unidirectional ones, where
+ *   packets[1] is 0 and a destination has only received. A flow whose two addresses are equal
+ *   contributes twice to the one host: no special case.
+ * With `tcp` (the tracker's side table, flow_cap records): tcp_state[bt_flow_tcp_state(flags[0],
+ *   flags[1], the tracker's flags)] += 1 for both contributions (BT_TCP_NONE counts too, so the
+ *   seven counts sum to flows[0] + flows[1]); syn_flows[0] += 1 when flags[r] has SYN,
+ *   syn_flows[1] += 1 when flags[1-r] has it; syn_packets, fin_packets and rst_packets of the
+ *   side record are added (mod 2^32). Without `tcp` all of these are 0 and tcp is never read.
+ * Order: hosts are numbered in order of first appearance: a host's number is the rank of its
+ *   lowest contribution index among all hosts' lowest contribution indices (the rule of the
+ *   per-batch table's flows), so hosts[h].first_flow is non-decreasing in h. hosts[h] is written
+ *   for h < host_cap only, endpoint_host[c] for c < 2 n_flows only; nothing is written at or
+ *   past those bounds, and nothing in the state or in `tcp` is written at all.
+ * Slots: opts->slots is a power of two >= 128; 0 = the smallest such power of two >= 4 flow_cap,
+ *   which needs flow_cap <= 2^29. When the hosts do not fit, overflow_endpoints != 0, every other
+ *   output but status, n_flows and slots is unspecified (but in bounds), and the caller repeats
+ *   the call with more slots. A table with exactly as many slots as hosts succeeds.
+ * As the top-K call: asynchronous on `stream` (NULL = the context's), no allocation, no host
+ *   synchronisation and no device-to-host read; the state's geometry comes from what the process
+ *   remembers of it, and on a header mismatch the kernels write status = 1, every other field of
+ *   *result 0 and nothing else. Grids are sized by flow_cap; threads at or past n_flows do
+ *   nothing. Scratch: bt_flow_track_hosts_scratch_bytes(flow_cap, slots) bytes of the caller's
+ *   device memory, 256-byte aligned, initialised by the call (one word per slot, one per
+ *   contribution, per-block partials). Exact and bit-identical from run to run: integer sums,
+ *   minima, maxima and ordered scans only.
+ * bt_flow_track_hosts_host: the same on the calling thread over a state in host memory (tcp, the
+ *   outputs and *result in host memory), bit-identical in every output.
+ * BT_E_INVALID_ARGUMENT, decided before the context or any HIP call: a null state, opts, out,
+ *   result or scratch; misalignment (state and scratch 256 bytes; result and hosts 8; tcp and
+ *   endpoint_host 4); slots not a power of two or below 128, or auto slots with flow_cap above
+ *   2^29; non-zero reserved fields; hosts == NULL with host_cap != 0; a state the process does
+ *   not know (host form: the header checks of the tracker's host forms), or one of 2^31 flows
+ *   (its last contribution index would be the empty slot word); scratch_bytes below the need;
+ *   then a null context. */
+typedef struct bt_flow_host_rec {      /* 128 B, 8-byte aligned */
+    uint8_t  addr[16];                 /* IPv4: 4 bytes in wire order, the rest zero; IPv6: 16 */
+    uint8_t  family;                   /* 4 or 6 */
+    uint8_t  pad[3];                   /* 0 */
+    uint32_t first_flow;               /* lowest flow number that has this host as an endpoint */
+    uint32_t flows[2];                 /* flows with the host as the key's first / second endpoint */
+    uint64_t packets[2], bytes[2];     /* [0] sent by the host, [1] sent to it */
+    uint64_t first_ts, last_ts;        /* min of its flows' first_ts, max of their last_ts */
+    uint32_t tcp_state[7];             /* its flows by bt_flow_tcp_state (index BT_TCP_*); 0 without tcp */
+    uint32_t syn_flows[2];             /* flows whose flags have SYN in the direction the host sends [0] / receives [1] */
+    uint32_t syn_packets, fin_packets, rst_packets;   /* sums of its flows' side records, mod 2^32 */
+} bt_flow_host_rec;
+typedef struct bt_flow_hosts_opts { uint32_t slots /* 0 = auto */, host_cap, reserved[2]; } bt_flow_hosts_opts;
+typedef struct bt_flow_hosts_result {  /* 64 B, device-visible, 8-byte aligned */
+    uint32_t n_flows, n_hosts, n_written, status;        /* n_written = min(n_hosts, host_cap); status as the tracker's */
+    uint32_t overflow_endpoints, slots, hosts_v4, hosts_v6;
+    uint64_t packets_total, bytes_total, reserved[2];    /* sums over the flows, mod 2^64 = sums of packets[0] / bytes[0] over all hosts */
+} bt_flow_hosts_result;
+typedef struct bt_flow_hosts_out {
+    bt_flow_host_rec* hosts;           /* optional when host_cap == 0; host_cap records */
+    uint32_t* endpoint_host;           /* optional, 2 * flow_cap entries: [2 f + role] = the host number of flow f's endpoint */
+    bt_flow_hosts_result* result;      /* required */
+} bt_flow_hosts_out;
+
+int  bt_flow_track_hosts_scratch_bytes(uint32_t flow_cap, uint32_t slots, uint64_t* bytes);   /* host only */
+int  bt_flow_track_hosts_device(bt_ctx* ctx, const void* state, const bt_flow_hosts_opts* opts,
+                                const bt_flow_tcp_rec* tcp /* optional, flow_cap */, void* scratch, uint64_t scratch_bytes,
+                                const bt_flow_hosts_out* out, void* stream);
+int  bt_flow_track_hosts_host(const void* state, uint64_t state_bytes, const bt_flow_hosts_opts* opts, const bt_flow_tcp_rec* tcp,
+                              const bt_flow_hosts_out* out);
 
 /* ---- pcap capture files ------------------------------------------------------------
  * Classic pcap (24-B global header, 16-B record headers), link type 1 (Ethernet), in all four

@@ -141,6 +141,20 @@ int  bt_time_flow_top(bt_ctx* ctx, const void* state, const bt_flow_top_opts* op
  * calling thread. top_total (optional): the sum of the last top's values. */
 int  bt_time_flow_top_host(bt_ctx* ctx, const bt_flow_track_rec* recs, uint32_t n_flows, uint32_t k, uint32_t iters,
                            float* copy_ms, float* sort_ms, uint64_t* top_total);
+/* bt_flow_track_hosts_device `iters` times on the context's stream over the same state; ms[i] =
+ * call i's kernels, from an event pair recorded by the first and the last kernel's own dispatches. */
+int  bt_time_flow_hosts(bt_ctx* ctx, const void* state, const bt_flow_hosts_opts* opts, const bt_flow_tcp_rec* tcp,
+                        void* scratch, uint64_t scratch_bytes, const bt_flow_hosts_out* out, uint32_t iters, float* ms);
+/* What the endpoint table replaces, `iters` times: copy_ms[i] = the header and the first n_flows
+ * records of the tracker at `state` (on the device, known to the process) and, with tcp, its
+ * n_flows side records copied to pinned host memory (wall clock, the wait included); group_ms[i] =
+ * bt_flow_track_hosts_host over them on the calling thread, into host_cap records and no
+ * endpoint_host. last (optional): the last result. sums (optional, six u64, mod 2^64) over the
+ * n_written records of the last run: packets[0]; packets[1]; bytes[0] ^ bytes[1]; flows[0] +
+ * flows[1]; tcp_state[j] * (j + 1) over j; first_ts ^ last_ts ^ (first_flow << 32 | syn_packets). */
+int  bt_time_flow_hosts_host(bt_ctx* ctx, const void* state, uint32_t n_flows, const bt_flow_tcp_rec* tcp,
+                             const bt_flow_hosts_opts* opts, uint32_t iters, float* copy_ms, float* group_ms,
+                             bt_flow_hosts_result* last, uint64_t* sums);
 /* A device-to-device hipMemcpyAsync of `bytes` on the context's stream, `iters` times, each
  * between an event pair: the ceiling for moving that many bytes on the device. */
 int  bt_time_copy_d2d(bt_ctx* ctx, void* dst, const void* src, uint64_t bytes, uint32_t iters, float* ms);

@@ -5,7 +5,8 @@ the file (the NetFlow / conntrack view of a capture).
 Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [--bidirectional] [--l3-only]
                                   [--top N] [--format csv|json] [--chunk-packets N]
                                   [--track [--idle SECONDS] [--flow-cap N] [--tcp [--closed-idle SECONDS]]
-                                           [--by bytes|packets|duration|syn|rst]]
+                                           [--by bytes|packets|duration|syn|rst]
+                                           [--hosts [--top N --by bytes|packets|flows]]]
   --filter         as tools/pcap_filter.py takes it; only passing packets are counted
   --bidirectional  both directions of a conversation are one flow (BT_FLOWTAB_BIDIRECTIONAL): the
                    listed source is the smaller endpoint, packets_rev / bytes_rev count the other direction
@@ -32,6 +33,13 @@ Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [-
                    earliest-seen flow first among equals: bytes (default), packets (both directions), duration
                    (last minus first packet time by the pcap record headers), syn or rst (with --tcp: packets with
                    SYN and no ACK, with RST)
+  --hosts          with --track: the endpoint view instead of the flow list (bt_flow_track_hosts_device, one query
+                   behind the last update): one line per address with the flows it is the first / second
+                   endpoint of, packets and bytes sent and received, first and last seen (seconds by the pcap
+                   record headers) and, with --tcp, its flows by connection state, the flows with SYN in the
+                   direction it sends / receives, and SYN / FIN / RST packets. Hosts come in order of first
+                   appearance; --top N keeps the N largest by --by bytes (sent + received, default), packets or
+                   flows, sorted here from the host records read back. Not with --idle.
 With --track and --top N, N <= 4096, the top is selected on the device (bt_flow_track_top_device behind the
 last update): still one wait, then only the N records (and N side records with --tcp) are read. A larger N
 downloads every record and sorts here, as the default path does.
@@ -63,6 +71,11 @@ K_HOST = 9   # enum bt_filter_kind
 COLUMNS = ("class", "src", "dst", "sport", "dport", "packets", "bytes", "packets_rev", "bytes_rev", "first", "last")
 TCP_COLUMNS = ("tcp_flags_fwd", "tcp_flags_rev", "tcp_state", "syn", "fin", "rst")
 U64_MAX = (1 << 64) - 1
+HOST_COLUMNS = ("address", "flows_src", "flows_dst", "packets_sent", "bytes_sent", "packets_received", "bytes_received",
+                "first_seen", "last_seen")
+HOST_TCP_COLUMNS = tuple("tcp_" + n for n in abi.TCP_STATE_NAMES) + ("syn_flows_sent", "syn_flows_received", "syn", "fin", "rst")
+HOSTS_BY = {"bytes": lambda r: r["bytes_sent"] + r["bytes_received"], "packets": lambda r: r["packets_sent"] + r["packets_received"],
+            "flows": lambda r: r["flows_src"] + r["flows_dst"]}
 TOP_BY = {"bytes": abi.FLOW_TOP_BYTES, "packets": abi.FLOW_TOP_PACKETS, "duration": abi.FLOW_TOP_DURATION,
           "syn": abi.FLOW_TOP_TCP_SYN, "rst": abi.FLOW_TOP_TCP_RST}
 
@@ -76,6 +89,22 @@ def describe(klass: int, key: bytes, v: list) -> dict:
             "dst": str(ipaddress.ip_address(key[alen:2 * alen])),
             "sport": int.from_bytes(p[0:2], "big") if ports else None, "dport": int.from_bytes(p[2:4], "big") if ports else None,
             "packets": v[0], "bytes": v[2], "packets_rev": v[1], "bytes_rev": v[3], "first": v[4], "last": v[5]}
+
+
+def describe_host(h, with_tcp: bool, unit: int, digits: int) -> dict:
+    """One --hosts output line from a bt_flow_host_rec."""
+    stamp = lambda v: f"{int(v) // unit}.{int(v) % unit:0{digits}d}"   # noqa: E731  exact: seconds, then the file's fraction
+    r = {"address": str(ipaddress.ip_address(h["addr"].tobytes()[:4 if int(h["family"]) == 4 else 16])),
+         "flows_src": int(h["flows"][0]), "flows_dst": int(h["flows"][1]),
+         "packets_sent": int(h["packets"][0]), "bytes_sent": int(h["bytes"][0]),
+         "packets_received": int(h["packets"][1]), "bytes_received": int(h["bytes"][1]),
+         "first_seen": stamp(h["first_ts"]), "last_seen": stamp(h["last_ts"])}
+    if with_tcp:
+        for k, name in enumerate(abi.TCP_STATE_NAMES):
+            r["tcp_" + name] = int(h["tcp_state"][k])
+        r["syn_flows_sent"], r["syn_flows_received"] = int(h["syn_flows"][0]), int(h["syn_flows"][1])
+        r["syn"], r["fin"], r["rst"] = int(h["syn_packets"]), int(h["fin_packets"]), int(h["rst_packets"])
+    return r
 
 
 def merge(table: dict, flows: np.ndarray, lo: int):
@@ -102,8 +131,8 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
     unit = 1_000_000_000 if info["nanosecond"] else 1_000_000
     starts = np.array([lo for lo, _ in parts] + [0], np.int64)
     timed = a.idle is not None
-    on_device = 0 < a.top <= abi.FLOW_TOP_MAX_K   # the top comes from the device (--idle with --top is refused)
-    stamped = timed or (on_device and a.by == "duration")
+    on_device = 0 < a.top <= abi.FLOW_TOP_MAX_K and not a.hosts   # the top comes from the device (--idle with --top is refused)
+    stamped = timed or (on_device and a.by == "duration") or a.hosts
     if stamped:   # a record's header is the 16 bytes before its data: ts_sec, ts_frac in the file's byte order
         head = np.stack([data[off - 16 + k] for k in range(8)], axis=1).astype(np.uint64) if len(off) else np.zeros((0, 8), np.uint64)
         order = (3, 2, 1, 0) if info["swapped"] else (0, 1, 2, 3)
@@ -151,6 +180,10 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         tneed = abi.flow_track_top_scratch_bytes(cap, a.top)
         d_tscratch, d_top, d_top_tcp, d_top_res = ctx.alloc(tneed), ctx.alloc(104 * a.top), ctx.alloc(16 * a.top), ctx.alloc(48)
         bufs += [d_tscratch, d_top, d_top_tcp, d_top_res]
+    if a.hosts:   # room for every host: two per flow
+        hneed = abi.flow_track_hosts_scratch_bytes(cap)
+        d_hscratch, d_hosts, d_hres = ctx.alloc(hneed), ctx.alloc(128 * 2 * cap), ctx.alloc(64)
+        bufs += [d_hscratch, d_hosts, d_hres]
     ctx.reserve(max_n)
     ctx.flow_track_init(d_state, lay["total"], cap, flags)
     for lo, hi in parts:
@@ -181,11 +214,23 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
     if on_device:   # behind the last update and side table update, on their stream
         ctx.flow_track_top(d_state, TOP_BY[a.by], a.top, d_tscratch, tneed, d_top_res, top=d_top, tcp=d_tcp if a.tcp else None,
                            top_tcp=d_top_tcp if a.tcp else None)
+    if a.hosts:   # one query at the end of the capture, behind the last update and side table update
+        ctx.flow_track_hosts(d_state, 2 * cap, d_hscratch, hneed, d_hres, hosts=d_hosts, tcp=d_tcp if a.tcp else None)
     ctx.synchronize()   # the one wait of the plain --track path
     hdr = abi.FlowTrackHdr.from_bytes(d_state.download(np.zeros(128, np.uint8))).as_dict()
     if hdr["overflow_packets"]:
         raise SystemExit(f"pcap_flows: more than --flow-cap {cap} flows at once")
-    if on_device:
+    if a.hosts:
+        totals["flows"] = hdr["n_flows"]
+        res = abi.FlowHostsResult.from_bytes(d_hres.download(np.zeros(64, np.uint8))).as_dict()
+        if res["status"] or res["overflow_endpoints"] or res["n_flows"] != hdr["n_flows"]:   # 4 flow_cap slots hold any 2 n_flows hosts
+            raise SystemExit("pcap_flows: the endpoint query did not see the tracker")
+        totals["hosts"], totals["hosts_v4"], totals["hosts_v6"] = res["n_hosts"], res["hosts_v4"], res["hosts_v6"]
+        if res["n_written"]:   # only the host records cross PCIe
+            digits = 9 if info["nanosecond"] else 6
+            rows += [describe_host(h, a.tcp, unit, digits)
+                     for h in d_hosts.download(np.zeros(128 * res["n_written"], np.uint8)).view(abi.FlowHostRec)]
+    elif on_device:
         totals["flows"] = hdr["n_flows"]   # not the lines printed
         res = abi.FlowTopResult.from_bytes(d_top_res.download(np.zeros(48, np.uint8))).as_dict()
         if res["status"] or res["n_flows"] != hdr["n_flows"]:
@@ -248,7 +293,8 @@ def main():
     ap.add_argument("--flow-cap", type=int, default=0)
     ap.add_argument("--tcp", action="store_true")
     ap.add_argument("--closed-idle", type=float, default=None, metavar="SECONDS")
-    ap.add_argument("--by", choices=tuple(TOP_BY), default=None)
+    ap.add_argument("--by", choices=tuple(TOP_BY) + ("flows",), default=None)
+    ap.add_argument("--hosts", action="store_true")
     a = ap.parse_args()
     if a.chunk_packets < 0 or a.top < 0:
         raise SystemExit("--chunk-packets / --top: want a positive count")
@@ -262,7 +308,13 @@ def main():
         raise SystemExit("--closed-idle: want a time in seconds >= 0, with --tcp and --idle")
     if a.flow_cap < 0:
         raise SystemExit("--flow-cap: want a positive count")
-    if a.by is not None and not (a.track and 0 < a.top <= abi.FLOW_TOP_MAX_K):
+    if a.hosts and (not a.track or a.idle is not None):
+        raise SystemExit("--hosts: only with --track, and without --idle")
+    if a.hosts and a.by is not None and (a.by not in HOSTS_BY or not a.top):
+        raise SystemExit("--hosts --by: bytes, packets or flows, with --top N")
+    if not a.hosts and a.by == "flows":
+        raise SystemExit("--by flows: only with --hosts")
+    if not a.hosts and a.by is not None and not (a.track and 0 < a.top <= abi.FLOW_TOP_MAX_K):
         raise SystemExit(f"--by: only with --track and --top N, N <= {abi.FLOW_TOP_MAX_K}")
     if a.by in ("syn", "rst") and not a.tcp:
         raise SystemExit("--by syn / rst: only with --tcp")
@@ -296,7 +348,11 @@ def main():
         ctx.close()
     rows = [describe(k[0], k[1], v) for k, v in table.items()] if tracked is None else tracked   # insertion order: by first packet
     columns = COLUMNS + (("first_ts", "last_ts") if a.idle is not None else ()) + (TCP_COLUMNS if a.tcp else ())
-    if a.top and not (a.track and a.top <= abi.FLOW_TOP_MAX_K):   # otherwise the device selected and ordered them
+    if a.hosts:   # host records in order of first appearance; a top is sorted here (stable: ties stay in that order)
+        columns = HOST_COLUMNS + (HOST_TCP_COLUMNS if a.tcp else ())
+        if a.top:
+            rows = sorted(rows, key=lambda r: -HOSTS_BY[a.by](r))[:a.top]
+    elif a.top and not (a.track and a.top <= abi.FLOW_TOP_MAX_K):   # otherwise the device selected and ordered them
         rows = sorted(rows, key=lambda r: (-(r["bytes"] + r["bytes_rev"]), r["first"]))[:a.top]
     if a.format == "csv":
         print(",".join(columns))
