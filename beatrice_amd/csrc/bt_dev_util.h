@@ -26,6 +26,16 @@ __device__ __forceinline__ uint32_t be16_of(const uint32_t* w, int i) {
     return (byte_of(w, i) << 8) | byte_of(w, i + 1);
 }
 
+// The slot words tab[0 .. slots) of a hash table to `empty` with 16-byte stores, a share per thread
+// of a grid of blocks of Threads threads; tab is 16-byte aligned and slots a multiple of 4 (of 128,
+// in every table here).
+template <uint32_t Threads>
+__device__ __forceinline__ void slots_fill(uint32_t* tab, uint32_t slots, uint32_t empty) {
+    u32x4* const q = reinterpret_cast<u32x4*>(tab);
+    const uint64_t nq = slots / 4u, step = (uint64_t)gridDim.x * Threads;
+    for (uint64_t x = (uint64_t)blockIdx.x * Threads + threadIdx.x; x < nq; x += step) q[x] = u32x4{empty, empty, empty, empty};
+}
+
 // K little-endian dwords starting at byte `a` of the LDS image (any alignment).
 template <int K>
 __device__ __forceinline__ void window(const uint32_t* lds, uint32_t a, uint32_t* out) {

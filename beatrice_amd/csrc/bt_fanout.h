@@ -124,42 +124,57 @@ inline bool fanout_args(const bt_batch* frames, const uint64_t* select, const bt
     return true;
 }
 
-// The flow key of a frame (DESIGN.md §2's walk over frame[0 .. len)): in[0 .. returned) and the
-// class. Every byte read lies below len.
-inline uint32_t flow_key_host(const uint8_t* f, uint32_t len, bool l3_only, uint8_t in[kFanInputMax], uint32_t* klass) {
-    *klass = BT_FLOW_NONE;
-    if (len < 14u) return 0;
+// The host's layer walk over frame[0 .. len) (DESIGN.md §2 as far as a flow key needs it), the one
+// copy under flow_key_host and flowtcp_frame_host (bt_flowtcp.h). Plain byte-wise C++ that shares
+// nothing with the device's walk (bt_flow_walk.h): it is what the device is held to. Every byte
+// read lies below len.
+struct FlowLayersHost {
+    bool v4, v6;        // a whole IPv4 / IPv6 header behind at most two tags
+    bool l4;            // protocol 6 or 17, its whole header (20 / 8 bytes) inside the frame, and for
+                        // IPv4 neither MF nor a fragment offset: the rule under which the key takes ports
+    uint32_t proto;     // IPv4 protocol / IPv6 next header (no extension headers are walked)
+    uint32_t o3, o4;    // where L3 and L4 start; o4 only with v4 or v6
+};
+
+inline FlowLayersHost flow_layers_host(const uint8_t* f, uint32_t len) {
+    FlowLayersHost L{};
+    if (len < 14u) return L;
     const auto be16 = [&](uint32_t o) { return (uint32_t)f[o] << 8 | f[o + 1]; };
     uint32_t et = be16(12), k = 0;
     while (k < 2u && (et == 0x8100u || et == 0x88A8u)) {
-        if (len < 18u + 4u * k) return 0;   // the tag, or the EtherType after it, is not in the frame
+        if (len < 18u + 4u * k) return L;   // the tag, or the EtherType after it, is not in the frame
         et = be16(16u + 4u * k);
         ++k;
     }
-    const uint32_t o3 = 14u + 4u * k;
-    if (et == 0x0800u) {
-        if (len - o3 < 20u) return 0;
-        memcpy(in, f + o3 + 12u, 8);
-        *klass = BT_FLOW_V4;
-        const uint32_t o4 = o3 + 4u * (f[o3] & 0xFu), proto = f[o3 + 9u];
-        const uint32_t need = proto == 6u ? 20u : proto == 17u ? 8u : 0u;
-        if (l3_only || !need || o4 > len || len - o4 < need || (be16(o3 + 6u) & 0x3FFFu)) return 8;
-        memcpy(in + 8, f + o4, 4);
-        *klass = BT_FLOW_V4_L4;
-        return 12;
+    L.o3 = 14u + 4u * k;
+    bool fragment = false;
+    if (et == 0x0800u && len - L.o3 >= 20u) {
+        L.v4 = true;
+        L.proto = f[L.o3 + 9u];
+        L.o4 = L.o3 + 4u * (f[L.o3] & 0xFu);
+        fragment = (be16(L.o3 + 6u) & 0x3FFFu) != 0;   // MF or a fragment offset: addresses only
+    } else if (et == 0x86DDu && len - L.o3 >= 40u) {
+        L.v6 = true;
+        L.proto = f[L.o3 + 6u];
+        L.o4 = L.o3 + 40u;
+    } else {
+        return L;
     }
-    if (et == 0x86DDu) {
-        if (len - o3 < 40u) return 0;
-        memcpy(in, f + o3 + 8u, 32);
-        *klass = BT_FLOW_V6;
-        const uint32_t o4 = o3 + 40u, nh = f[o3 + 6u];
-        const uint32_t need = nh == 6u ? 20u : nh == 17u ? 8u : 0u;
-        if (l3_only || !need || len - o4 < need) return 32;
-        memcpy(in + 32, f + o4, 4);
-        *klass = BT_FLOW_V6_L4;
-        return 36;
-    }
-    return 0;
+    const uint32_t need = L.proto == 6u ? 20u : L.proto == 17u ? 8u : 0u;
+    L.l4 = need && !fragment && L.o4 <= len && len - L.o4 >= need;
+    return L;
+}
+
+// The flow key of a frame: in[0 .. returned) and the class. Every byte read lies below len.
+inline uint32_t flow_key_host(const uint8_t* f, uint32_t len, bool l3_only, uint8_t in[kFanInputMax], uint32_t* klass) {
+    const FlowLayersHost L = flow_layers_host(f, len);
+    const bool ports = L.l4 && !l3_only;
+    *klass = L.v4 ? (ports ? BT_FLOW_V4_L4 : BT_FLOW_V4) : L.v6 ? (ports ? BT_FLOW_V6_L4 : BT_FLOW_V6) : BT_FLOW_NONE;
+    if (!L.v4 && !L.v6) return 0;
+    const uint32_t na = L.v4 ? 8u : 32u;   // both addresses: L3 bytes 12 .. 19 / 8 .. 39
+    memcpy(in, f + L.o3 + (L.v4 ? 12u : 8u), na);
+    if (ports) memcpy(in + na, f + L.o4, 4);
+    return ports ? na + 4u : na;
 }
 
 // Toeplitz hash of in[0 .. n) (n <= 36) under a 40-byte key, MSB first: for every set bit i of

@@ -7,7 +7,8 @@
 // look-back, no spin and no global atomic, so every output is the same from run to run.
 //   bt_fanout_keys     one block of 8 waves per chunk of 256 tiles (16,384 packets), lane =
 //                      packet, wave w has tiles 32w .. 32w + 31 of the chunk. A lane walks its
-//                      frame's layers with two to four loads at the frame's own
+//                      frame's layers (flow_key, bt_flow_walk.h, which the flow
+//                      table and the TCP side table share) with two to four loads at the frame's own
 //                      alignment: bytes 12..27 (EtherType, up to two tags, the IPv4 IHL byte),
 //                      16 bytes from L3 + 4 (flags, protocol / next header, addresses), the
 //                      rest of the IPv6 addresses, the ports. The Toeplitz hash of the key is
@@ -26,8 +27,9 @@
 //                      among its queue's packets of the tile is a popcount below its lane.
 // Lanes at or past n never load. A frame byte is read only below a.bytes (fan_read_end: inside
 // the 16-B granules of [base, base + bytes)), and reads as zero at or past it.
-#include "bt_dev_util.h"
+#include "bt_flow_walk.h"
 #include "bt_hip_launch.h"
+#include "bt_wave.h"
 #include "bt_fanout.h"
 
 namespace bt {
@@ -36,99 +38,6 @@ namespace {
 
 constexpr uint32_t kFanThreads = kFanWaves * 64u;
 constexpr uint32_t kFanWaveTiles = kFanChunkTiles / kFanWaves;
-
-typedef u32x4 u32x4_any __attribute__((aligned(1)));   // loads at any byte alignment
-typedef u32x2 u32x2_any __attribute__((aligned(1)));
-typedef uint32_t u32_any __attribute__((aligned(1)));
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1)
-        v += ((uint64_t)__shfl_xor((uint32_t)(v >> 32), o) << 32) | __shfl_xor((uint32_t)v, o);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// W dwords (1, 2 or 4) from offset x of base, little-endian; `on` false: zeros, nothing loaded.
-template <int W>
-__device__ __forceinline__ void load_at(const FanoutArgs& a, uint64_t x, bool on, uint32_t* v) {
-#pragma unroll
-    for (int k = 0; k < W; ++k) v[k] = 0u;
-    if (!on || x >= a.bytes) return;
-    if (a.bytes - x >= 4u * W) {
-        const uint8_t* p = a.base + x;
-        if (W == 4) {
-            const u32x4 t = *reinterpret_cast<const u32x4_any*>(p);
-            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-        } else if (W == 2) {
-            const u32x2 t = *reinterpret_cast<const u32x2_any*>(p);
-            v[0] = t.x; v[1] = t.y;
-        } else {
-            v[0] = *reinterpret_cast<const u32_any*>(p);
-        }
-        return;
-    }
-    const uint32_t have = (uint32_t)(a.bytes - x);   // 1 .. 4 W - 1 bytes before the limit
-#pragma unroll
-    for (int b = 0; b < 4 * W; ++b)
-        if ((uint32_t)b < have) v[b >> 2] |= (uint32_t)a.base[x + b] << (8 * (b & 3));
-}
-
-__device__ __forceinline__ uint32_t be32(uint32_t le) { return __builtin_bswap32(le); }
-
-__device__ __forceinline__ bool is_tag(uint32_t et) { return et == 0x8100u || et == 0x88A8u; }
-
-// The flow key of the frame at [off, off + len) as big-endian words w[0 .. nw), and its class.
-__device__ __forceinline__ uint32_t flow_key(const FanoutArgs& a, uint64_t off, uint32_t len, bool live, uint32_t (&w)[9],
-                                             uint32_t& nw) {
-    live = live && len >= 14u;
-    uint32_t A[4];   // frame bytes 12 .. 27
-    load_at<4>(a, off + 12u, live, A);
-    uint32_t et = be16_of(A, 0), k = 0;
-    bool stop = !live;
-#pragma unroll
-    for (uint32_t j = 0; j < 2u; ++j) {
-        if (!stop && is_tag(et)) {
-            if (len < 18u + 4u * j) stop = true;   // the tag, or the EtherType after it, is not in the frame
-            else { et = be16_of(A, 4 + 4 * (int)j); k = j + 1u; }
-        }
-    }
-    const uint32_t o3 = 14u + 4u * k;
-    const uint32_t b0 = k == 0u ? byte_of(A, 2) : k == 1u ? byte_of(A, 6) : byte_of(A, 10);   // frame[o3]
-    const bool v4 = !stop && et == 0x0800u && len - o3 >= 20u;
-    const bool v6 = !stop && et == 0x86DDu && len - o3 >= 40u;
-    uint32_t B[4], C[4], D[2], P[1];
-    load_at<4>(a, off + o3 + 4u, v4 || v6, B);    // L3 bytes 4 .. 19
-    load_at<4>(a, off + o3 + 20u, v6, C);         // IPv6 bytes 20 .. 35
-    load_at<2>(a, off + o3 + 36u, v6, D);         // IPv6 bytes 36 .. 39 and the ports behind the header
-    const uint32_t proto = v4 ? byte_of(B, 5) : byte_of(B, 2);   // IPv4 protocol / IPv6 next header
-    const uint32_t need = proto == 6u ? 20u : proto == 17u ? 8u : 0u;
-    const uint32_t o4 = v4 ? o3 + 4u * (b0 & 0xFu) : o3 + 40u;
-    bool l4 = (v4 || v6) && !a.l3_only && need && o4 <= len && len - o4 >= need;
-    if (v4 && (be16_of(B, 2) & 0x3FFFu)) l4 = false;   // MF or a fragment offset: addresses only
-    load_at<1>(a, off + o4, v4 && l4, P);
-#pragma unroll
-    for (int d = 0; d < 9; ++d) w[d] = 0u;
-    if (v4) {
-        w[0] = be32(B[2]); w[1] = be32(B[3]);
-        if (l4) w[2] = be32(P[0]);
-        nw = l4 ? 3u : 2u;
-        return l4 ? BT_FLOW_V4_L4 : BT_FLOW_V4;
-    }
-    if (v6) {
-        w[0] = be32(B[1]); w[1] = be32(B[2]); w[2] = be32(B[3]);
-        w[3] = be32(C[0]); w[4] = be32(C[1]); w[5] = be32(C[2]); w[6] = be32(C[3]);
-        w[7] = be32(D[0]);
-        if (l4) w[8] = be32(D[1]);
-        nw = l4 ? 9u : 8u;
-        return l4 ? BT_FLOW_V6_L4 : BT_FLOW_V6;
-    }
-    nw = 0u;
-    return BT_FLOW_NONE;
-}
 
 // Toeplitz, MSB first. Words at or past nw are zero and add nothing; a word no lane of the wave
 // has ends the loop.

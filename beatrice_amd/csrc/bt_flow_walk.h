@@ -1,8 +1,10 @@
 // bt_flow_walk.h — the flow kernels' layer walk (DESIGN.md §2 as far as a flow key needs it), once,
 // for any argument type that derives from FrameSrc (`bytes` = fan_read_end): where L3 and L4
-// start, whether the frame holds a whole L4 header, the fragment rule, and the key words. Device
-// code only. bt_flowtcp.hip uses it; bt_fanout.hip and bt_flowtab.hip still hold their own copies
-// of load_at and flow_key, word for word the same walk (a change to one is a change to all three).
+// start, whether the frame holds a whole L4 header, the fragment rule, the key words and their
+// canonical direction. Device code only, and the device's only copy: bt_fanout.hip, bt_flowtab.hip
+// and bt_flowtcp.hip all walk a frame through flow_layers and flow_key_words. The host's walk is
+// flow_layers_host (bt_fanout.h), kept apart on purpose: it is the oracle the tests hold this one
+// to (tests/test_gpu_flow_walk.py).
 #pragma once
 
 #include "bt_dev_util.h"
@@ -110,12 +112,26 @@ __device__ __forceinline__ uint32_t flow_key_words(const A& a, uint64_t off, con
     return BT_FLOW_NONE;
 }
 
+// Both steps, for a caller that needs the key alone: the key and class of the frame at
+// [off, off + len) under a.l3_only.
+template <class A>
+__device__ __forceinline__ uint32_t flow_key(const A& a, uint64_t off, uint32_t len, bool live, uint32_t (&w)[9], uint32_t& nw) {
+    FlowLayers L;
+    flow_layers(a, off, len, live, L);
+    return flow_key_words(a, off, L, L.l4 && !a.l3_only, w, nw);
+}
+
 // BT_FLOWTAB_BIDIRECTIONAL: endpoint A (source address, source port) against B as byte strings,
-// which is the order of the big-endian words. 1: A > B, the table stores the endpoints swapped.
-__device__ __forceinline__ uint32_t flow_direction(uint32_t klass, const uint32_t (&w)[9]) {
+// which is the order of the big-endian words. A > B: direction 1, and w leaves with the endpoints
+// exchanged, which is the form the table stores.
+__device__ __forceinline__ uint32_t flow_canonical(uint32_t klass, uint32_t (&w)[9]) {
     if (klass == BT_FLOW_V4 || klass == BT_FLOW_V4_L4) {
         const uint32_t sp = w[2] >> 16, dp = w[2] & 0xFFFFu;   // both 0 without ports
-        return (w[0] < w[1] || (w[0] == w[1] && sp <= dp)) ? 0u : 1u;
+        if (w[0] < w[1] || (w[0] == w[1] && sp <= dp)) return 0u;
+        const uint32_t t = w[0];
+        w[0] = w[1]; w[1] = t;
+        w[2] = dp << 16 | sp;
+        return 1u;
     }
     if (klass == BT_FLOW_V6 || klass == BT_FLOW_V6_L4) {
         int c = 0;   // the first differing word decides
@@ -123,9 +139,21 @@ __device__ __forceinline__ uint32_t flow_direction(uint32_t klass, const uint32_
         for (int d = 0; d < 4; ++d)
             if (c == 0 && w[d] != w[d + 4]) c = w[d] < w[d + 4] ? -1 : 1;
         const uint32_t sp = w[8] >> 16, dp = w[8] & 0xFFFFu;
-        return (c < 0 || (c == 0 && sp <= dp)) ? 0u : 1u;
+        if (c < 0 || (c == 0 && sp <= dp)) return 0u;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) { const uint32_t t = w[d]; w[d] = w[d + 4]; w[d + 4] = t; }
+        w[8] = dp << 16 | sp;
+        return 1u;
     }
     return 0u;
+}
+
+// The direction alone: w stays as it is.
+__device__ __forceinline__ uint32_t flow_direction(uint32_t klass, const uint32_t (&w)[9]) {
+    uint32_t t[9];
+#pragma unroll
+    for (int d = 0; d < 9; ++d) t[d] = w[d];
+    return flow_canonical(klass, t);
 }
 
 }  // namespace

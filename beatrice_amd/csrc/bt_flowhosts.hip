@@ -50,8 +50,9 @@
 // arrive singly, combined in a wave, through the LDS cache or directly. The scratch holds the only
 // values that vary. Across the XCDs' L2s: the kernels read only atomics' results and data written
 // by earlier kernels.
-#include "bt_dev_util.h"
+#include "bt_flowtrack_dev.h"
 #include "bt_hip_launch.h"
+#include "bt_wave.h"
 #include "bt_flowhosts.h"
 
 namespace bt {
@@ -61,39 +62,6 @@ namespace {
 typedef u32x4 u32x4_a8 __attribute__((aligned(8)));   // a record is 8-byte aligned: 104 B = six of these and a u64
 typedef u32x4 u32x4_a4 __attribute__((aligned(4)));   // a side record is 4-byte aligned
 typedef u32x2 u32x2_a4 __attribute__((aligned(4)));   // as endpoint_host is
-
-__device__ __forceinline__ bool hdr_ok(const FlowhostsArgs& a) {   // the state is the tracker the host took the call for
-    const bt_flow_track_hdr* const h = a.hdr;
-    return h->magic == BT_FLOW_TRACK_MAGIC && h->flags == a.flags && h->flow_cap == a.flow_cap && h->slots == a.state_slots &&
-           h->n_flows <= a.flow_cap;
-}
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1)
-        v += ((uint64_t)__shfl_xor((uint32_t)(v >> 32), o) << 32) | __shfl_xor((uint32_t)v, o);
-    return v;
-}
-
-__device__ __forceinline__ uint64_t wave_min64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t y = ((uint64_t)__shfl_xor((uint32_t)(v >> 32), o) << 32) | __shfl_xor((uint32_t)v, o);
-        v = y < v ? y : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint64_t wave_max64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t y = ((uint64_t)__shfl_xor((uint32_t)(v >> 32), o) << 32) | __shfl_xor((uint32_t)v, o);
-        v = y > v ? y : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // The first ten words of record f: the 36 key bytes, the class, zeros.
 __device__ __forceinline__ void head_load(const bt_flow_track_rec* r, uint32_t (&w)[10]) {
@@ -188,13 +156,9 @@ static_assert(kFhCache == kFkThreads, "one thread per entry of the sum pass's LD
 
 // H0: the control block, every slot empty.
 __global__ __launch_bounds__(kFkThreads) void bt_flowhosts_begin(FlowhostsArgs a) {
-    {   // slots is a multiple of 128
-        u32x4* const q = reinterpret_cast<u32x4*>(a.tab);
-        const uint64_t nq = a.slots / 4u, step = (uint64_t)gridDim.x * kFkThreads;
-        for (uint64_t x = (uint64_t)blockIdx.x * kFkThreads + threadIdx.x; x < nq; x += step) q[x] = u32x4{kFhEmpty, kFhEmpty, kFhEmpty, kFhEmpty};
-    }
+    slots_fill<kFkThreads>(a.tab, a.slots, kFhEmpty);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const bool ok = hdr_ok(a);
+        const bool ok = hdr_ok(a, a.state_slots);
         *a.ctl = FhCtl{ok ? 1u : 0u, ok ? a.hdr->n_flows : 0u, {0u, 0u}};
     }
 }

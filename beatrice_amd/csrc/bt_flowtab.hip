@@ -5,12 +5,12 @@
 // Six launches over the caller's scratch (bt_flowtab.h), lane = packet, one block of 8 waves per
 // chunk of 256 tiles as bt_fanout_keys. No lane ever waits for another lane, wave or block:
 // there is no spin, no flag and no look-back, and every loop has a bound in its head.
-//   bt_flowtab_keys    the fan-out's layer walk (flow_key below is bt_fanout.hip's, kept equal by
-//                      hand), the canonical direction when bidirectional, a probe hash of the key
-//                      words and the class; an FtFlow per selected packet with a key (its key,
-//                      and the sums of a flow that has this packet alone), an owner word per
-//                      packet (a sentinel, or "pending"), the chunk's sums. The grid also sets
-//                      the slots to empty, a share per block.
+//   bt_flowtab_keys    the fan-out's layer walk and key (flow_key, bt_flow_walk.h: the one copy
+//                      both use), the canonical direction when bidirectional (flow_canonical,
+//                      same header), a probe hash of the key words and the class; an FtFlow per
+//                      selected packet with a key (its key, and the sums of a flow that has this
+//                      packet alone), an owner word per packet (a sentinel, or "pending"), the
+//                      chunk's sums. The grid also sets the slots to empty, a share per block.
 //   bt_flowtab_insert  open addressing, linear probing, at most `slots` steps. A slot is one word;
 //                      it is claimed by a device-scope atomicCAS from empty to the packet's index,
 //                      and the claiming packet's FtFlow is from then on the flow's entry: its key
@@ -34,8 +34,9 @@
 // packets whichever of them came first, and the flow's number is the rank of its first packet,
 // which depends on the minima alone. The scratch holds the only values that vary. Across the
 // XCDs' L2s: the kernels read only atomics' results and data written by earlier kernels.
-#include "bt_dev_util.h"
+#include "bt_flow_walk.h"
 #include "bt_hip_launch.h"
+#include "bt_wave.h"
 #include "bt_flowtab.h"
 
 namespace bt {
@@ -44,127 +45,6 @@ namespace {
 
 constexpr uint32_t kFtThreads = kFtWaves * 64u;
 constexpr uint32_t kFtWaveTiles = kFtChunkTiles / kFtWaves;
-
-typedef u32x4 u32x4_any __attribute__((aligned(1)));   // loads at any byte alignment
-typedef u32x2 u32x2_any __attribute__((aligned(1)));
-typedef uint32_t u32_any __attribute__((aligned(1)));
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1)
-        v += ((uint64_t)__shfl_xor((uint32_t)(v >> 32), o) << 32) | __shfl_xor((uint32_t)v, o);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// load_at, is_tag and flow_key are bt_fanout.hip's, word for word but for the argument type:
-// the key and class of a packet are those of bt_flow_fanout_device. A change to either copy is
-// a change to both (tests/test_gpu_flowtab.py holds this one to the same restatement).
-template <int W>
-__device__ __forceinline__ void load_at(const FlowtabArgs& a, uint64_t x, bool on, uint32_t* v) {
-#pragma unroll
-    for (int k = 0; k < W; ++k) v[k] = 0u;
-    if (!on || x >= a.bytes) return;
-    if (a.bytes - x >= 4u * W) {
-        const uint8_t* p = a.base + x;
-        if (W == 4) {
-            const u32x4 t = *reinterpret_cast<const u32x4_any*>(p);
-            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-        } else if (W == 2) {
-            const u32x2 t = *reinterpret_cast<const u32x2_any*>(p);
-            v[0] = t.x; v[1] = t.y;
-        } else {
-            v[0] = *reinterpret_cast<const u32_any*>(p);
-        }
-        return;
-    }
-    const uint32_t have = (uint32_t)(a.bytes - x);   // 1 .. 4 W - 1 bytes before the limit
-#pragma unroll
-    for (int b = 0; b < 4 * W; ++b)
-        if ((uint32_t)b < have) v[b >> 2] |= (uint32_t)a.base[x + b] << (8 * (b & 3));
-}
-
-__device__ __forceinline__ uint32_t be32(uint32_t le) { return __builtin_bswap32(le); }
-
-__device__ __forceinline__ bool is_tag(uint32_t et) { return et == 0x8100u || et == 0x88A8u; }
-
-// The flow key of the frame at [off, off + len) as big-endian words w[0 .. nw), and its class.
-__device__ __forceinline__ uint32_t flow_key(const FlowtabArgs& a, uint64_t off, uint32_t len, bool live, uint32_t (&w)[9],
-                                             uint32_t& nw) {
-    live = live && len >= 14u;
-    uint32_t A[4];   // frame bytes 12 .. 27
-    load_at<4>(a, off + 12u, live, A);
-    uint32_t et = be16_of(A, 0), k = 0;
-    bool stop = !live;
-#pragma unroll
-    for (uint32_t j = 0; j < 2u; ++j) {
-        if (!stop && is_tag(et)) {
-            if (len < 18u + 4u * j) stop = true;   // the tag, or the EtherType after it, is not in the frame
-            else { et = be16_of(A, 4 + 4 * (int)j); k = j + 1u; }
-        }
-    }
-    const uint32_t o3 = 14u + 4u * k;
-    const uint32_t b0 = k == 0u ? byte_of(A, 2) : k == 1u ? byte_of(A, 6) : byte_of(A, 10);   // frame[o3]
-    const bool v4 = !stop && et == 0x0800u && len - o3 >= 20u;
-    const bool v6 = !stop && et == 0x86DDu && len - o3 >= 40u;
-    uint32_t B[4], C[4], D[2], P[1];
-    load_at<4>(a, off + o3 + 4u, v4 || v6, B);    // L3 bytes 4 .. 19
-    load_at<4>(a, off + o3 + 20u, v6, C);         // IPv6 bytes 20 .. 35
-    load_at<2>(a, off + o3 + 36u, v6, D);         // IPv6 bytes 36 .. 39 and the ports behind the header
-    const uint32_t proto = v4 ? byte_of(B, 5) : byte_of(B, 2);   // IPv4 protocol / IPv6 next header
-    const uint32_t need = proto == 6u ? 20u : proto == 17u ? 8u : 0u;
-    const uint32_t o4 = v4 ? o3 + 4u * (b0 & 0xFu) : o3 + 40u;
-    bool l4 = (v4 || v6) && !a.l3_only && need && o4 <= len && len - o4 >= need;
-    if (v4 && (be16_of(B, 2) & 0x3FFFu)) l4 = false;   // MF or a fragment offset: addresses only
-    load_at<1>(a, off + o4, v4 && l4, P);
-#pragma unroll
-    for (int d = 0; d < 9; ++d) w[d] = 0u;
-    if (v4) {
-        w[0] = be32(B[2]); w[1] = be32(B[3]);
-        if (l4) w[2] = be32(P[0]);
-        nw = l4 ? 3u : 2u;
-        return l4 ? BT_FLOW_V4_L4 : BT_FLOW_V4;
-    }
-    if (v6) {
-        w[0] = be32(B[1]); w[1] = be32(B[2]); w[2] = be32(B[3]);
-        w[3] = be32(C[0]); w[4] = be32(C[1]); w[5] = be32(C[2]); w[6] = be32(C[3]);
-        w[7] = be32(D[0]);
-        if (l4) w[8] = be32(D[1]);
-        nw = l4 ? 9u : 8u;
-        return l4 ? BT_FLOW_V6_L4 : BT_FLOW_V6;
-    }
-    nw = 0u;
-    return BT_FLOW_NONE;
-}
-
-// BT_FLOWTAB_BIDIRECTIONAL: endpoint A (source address, source port) against B as byte strings,
-// which is the order of the big-endian words. A > B: swapped, direction 1.
-__device__ __forceinline__ uint32_t canonical(uint32_t klass, uint32_t (&w)[9]) {
-    if (klass == BT_FLOW_V4 || klass == BT_FLOW_V4_L4) {
-        const uint32_t sp = w[2] >> 16, dp = w[2] & 0xFFFFu;   // both 0 without ports
-        if (w[0] < w[1] || (w[0] == w[1] && sp <= dp)) return 0u;
-        const uint32_t t = w[0];
-        w[0] = w[1]; w[1] = t;
-        w[2] = dp << 16 | sp;
-        return 1u;
-    }
-    if (klass == BT_FLOW_V6 || klass == BT_FLOW_V6_L4) {
-        int c = 0;   // the first differing word decides
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-            if (c == 0 && w[d] != w[d + 4]) c = w[d] < w[d + 4] ? -1 : 1;
-        const uint32_t sp = w[8] >> 16, dp = w[8] & 0xFFFFu;
-        if (c < 0 || (c == 0 && sp <= dp)) return 0u;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) { const uint32_t t = w[d]; w[d] = w[d + 4]; w[d + 4] = t; }
-        w[8] = dp << 16 | sp;
-        return 1u;
-    }
-    return 0u;
-}
 
 // The probe hash: a fixed mix of the class and the nine key words (zero past the class's length),
 // nothing the caller supplies but the key bytes goes in.
@@ -197,11 +77,7 @@ __device__ __forceinline__ void key_load(const FtFlow* k, uint32_t (&v)[12]) {
 __global__ __launch_bounds__(kFtThreads) void bt_flowtab_keys(FlowtabArgs a) {
     __shared__ uint32_t red[kFtWaves][4];
     const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-    {   // every slot empty; slots is a multiple of 128
-        u32x4* const q = reinterpret_cast<u32x4*>(a.tab);
-        const uint64_t nq = a.slots / 4u, step = (uint64_t)gridDim.x * kFtThreads;
-        for (uint64_t x = (uint64_t)c * kFtThreads + tid; x < nq; x += step) q[x] = u32x4{kFtEmpty, kFtEmpty, kFtEmpty, kFtEmpty};
-    }
+    slots_fill<kFtThreads>(a.tab, a.slots, kFtEmpty);
     if (c >= a.nchunks) return;   // a block that only initialises slots
 
     uint32_t nsel = 0, nnone = 0, bnone = 0, bkeyed = 0;   // nsel, nnone wave-uniform; the byte sums per lane
@@ -219,7 +95,7 @@ __global__ __launch_bounds__(kFtThreads) void bt_flowtab_keys(FlowtabArgs a) {
         uint32_t w[9], nw;
         const uint32_t klass = flow_key(a, off, len, sel, w, nw);
         const bool keyed = sel && klass != BT_FLOW_NONE;
-        const uint32_t dir = a.bidir ? canonical(klass, w) : 0u;
+        const uint32_t dir = a.bidir ? flow_canonical(klass, w) : 0u;
         const uint32_t blen = len > 0xFFFFu ? 0xFFFFu : len;
         if (in) a.pslot[i] = !sel ? BT_FLOW_ID_UNSELECTED : keyed ? kFtPending : BT_FLOW_ID_NONE;
         if (keyed) {
@@ -412,8 +288,8 @@ __global__ __launch_bounds__(kFtThreads) void bt_flowtab_rank(FlowtabArgs a) {
                 key_load(&fl, key);
                 uint64_t* const o = reinterpret_cast<uint64_t*>(a.flows + id);   // 80 B = ten words
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = (uint64_t)be32(key[2 * j + 1]) << 32 | be32(key[2 * j]);   // wire order
-                o[4] = (uint64_t)(key[9] & 0xFFu) << 32 | be32(key[8]);
+                for (int j = 0; j < 4; ++j) o[j] = (uint64_t)fw_be32(key[2 * j + 1]) << 32 | fw_be32(key[2 * j]);   // wire order
+                o[4] = (uint64_t)(key[9] & 0xFFu) << 32 | fw_be32(key[8]);
                 o[5] = (uint64_t)fl.last << 32 | i;
                 o[6] = (uint64_t)fl.packets[1] << 32 | fl.packets[0];
                 o[7] = fl.bytes[0];

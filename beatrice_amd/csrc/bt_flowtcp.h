@@ -94,31 +94,13 @@ inline bool flowtcp_host_args(const uint8_t* base, const bt_pkt_desc* desc, uint
     return true;
 }
 
-// Does frame[0 .. len) hold a whole TCP header under the flow key's rule (flow_key_host's walk: at
-// most two tags, no IPv6 extension headers, no IPv4 fragment)? *flags = byte 13 of that header.
-// Every byte read lies below len.
+// Does frame[0 .. len) hold a whole TCP header under the flow key's rule (flow_layers_host,
+// bt_fanout.h: at most two tags, no IPv6 extension headers, no IPv4 fragment)? *flags = byte 13 of
+// that header. Every byte read lies below len.
 inline bool flowtcp_frame_host(const uint8_t* f, uint32_t len, uint32_t* flags) {
-    if (len < 14u) return false;
-    const auto be16 = [&](uint32_t o) { return (uint32_t)f[o] << 8 | f[o + 1]; };
-    uint32_t et = be16(12), k = 0;
-    while (k < 2u && (et == 0x8100u || et == 0x88A8u)) {
-        if (len < 18u + 4u * k) return false;
-        et = be16(16u + 4u * k);
-        ++k;
-    }
-    const uint32_t o3 = 14u + 4u * k;
-    uint32_t o4 = 0;
-    if (et == 0x0800u) {
-        if (len - o3 < 20u || f[o3 + 9u] != 6u || (be16(o3 + 6u) & 0x3FFFu)) return false;
-        o4 = o3 + 4u * (f[o3] & 0xFu);
-    } else if (et == 0x86DDu) {
-        if (len - o3 < 40u || f[o3 + 6u] != 6u) return false;
-        o4 = o3 + 40u;
-    } else {
-        return false;
-    }
-    if (o4 > len || len - o4 < 20u) return false;
-    *flags = f[o4 + 13u];
+    const FlowLayersHost L = flow_layers_host(f, len);
+    if (!L.l4 || L.proto != 6u) return false;
+    *flags = f[L.o4 + 13u];
     return true;
 }
 

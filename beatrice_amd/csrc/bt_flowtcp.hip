@@ -25,6 +25,7 @@
 // set of packets whatever the order, so it is the same from run to run.
 #include "bt_flow_walk.h"
 #include "bt_hip_launch.h"
+#include "bt_wave.h"
 #include "bt_flowtcp.h"
 
 namespace bt {
@@ -35,11 +36,6 @@ constexpr uint32_t kTcpThreads = kFtWaves * 64u;
 constexpr uint32_t kTcpWaveTiles = kFtChunkTiles / kFtWaves;
 
 constexpr uint32_t kTcpNoFlow = 0xFFFFFFFFu;   // no pending counts (a flow number is below flow_cap <= 2^32 - 1)
-
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ void add_counts(bt_flow_tcp_rec* rec, uint32_t s, uint32_t f, uint32_t r) {
     if (s) atomicAdd(&rec->syn_packets, s);

@@ -28,8 +28,9 @@
 // tells the next goes through the kernel boundary, and every loop has its bound in its head. Why
 // the outputs are the same from run to run: the histograms and `total` are integer sums, the
 // candidates' places come from ordered scans, and the sort's key (value, id) is total.
-#include "bt_dev_util.h"
+#include "bt_flowtrack_dev.h"
 #include "bt_hip_launch.h"
+#include "bt_wave.h"
 #include "bt_flowtop.h"
 
 namespace bt {
@@ -38,53 +39,6 @@ namespace {
 
 constexpr uint32_t kSortWaves = kTopSortThreads / 64u;
 constexpr uint64_t kSpan = (uint64_t)kFkThreads * kTopUnroll;   // flows a block of a grid-stride pass takes per step
-
-__device__ __forceinline__ bool hdr_ok(const FlowtopArgs& a) {   // the state is the tracker the host took the call for
-    const bt_flow_track_hdr* const h = a.hdr;
-    return h->magic == BT_FLOW_TRACK_MAGIC && h->flags == a.flags && h->flow_cap == a.flow_cap && h->slots == a.slots &&
-           h->n_flows <= a.flow_cap;
-}
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1)
-        v += ((uint64_t)__shfl_xor((uint32_t)(v >> 32), o) << 32) | __shfl_xor((uint32_t)v, o);
-    return v;
-}
-
-template <uint32_t kWaves>
-__device__ __forceinline__ uint64_t block_sum64(uint64_t v, uint64_t* sh) {   // the sum of v over the block, to every thread
-    v = wave_sum64(v);
-    if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint64_t tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kWaves; ++w) tot += sh[w];
-    __syncthreads();
-    return tot;
-}
-
-// The exclusive scan of v over a block of kWaves waves, and the sum in *total; sh: kWaves words.
-template <uint32_t kWaves>
-__device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* sh, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    uint32_t incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o);
-        if (lane >= (uint32_t)o) incl += y;
-    }
-    if (lane == 63u) sh[wid] = incl;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kWaves; ++w) {
-        const uint32_t x = sh[w];
-        pre += w < wid ? x : 0u;
-        tot += x;
-    }
-    __syncthreads();
-    *total = tot;
-    return pre + incl - v;
-}
 
 // Every lane with `on` counts in bin d of the block's LDS histogram. Called by whole waves. The
 // lanes that agree with the first counting lane add once for all of them.
@@ -107,20 +61,6 @@ __device__ __forceinline__ void hist_flush(const uint32_t* h, uint32_t* global) 
     if (c) atomicAdd(&global[threadIdx.x], c);
 }
 
-__device__ __forceinline__ void rec_copy(bt_flow_track_rec* dst, const bt_flow_track_rec* src) {   // 104 B = 13 words
-    const uint64_t* const q = reinterpret_cast<const uint64_t*>(src);
-    uint64_t* const o = reinterpret_cast<uint64_t*>(dst);
-#pragma unroll
-    for (int j = 0; j < 13; ++j) o[j] = q[j];
-}
-
-__device__ __forceinline__ void tcp_copy(bt_flow_tcp_rec* dst, const bt_flow_tcp_rec* src) {   // 16 B, 4-byte aligned
-    const uint32_t* const q = reinterpret_cast<const uint32_t*>(src);
-    uint32_t* const o = reinterpret_cast<uint32_t*>(dst);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = q[j];
-}
-
 // Does (xv, xi) stand before (yv, yi) in the top's order?
 __device__ __forceinline__ bool before(uint64_t xv, uint32_t xi, uint64_t yv, uint32_t yi) {
     return xv != yv ? xv > yv : xi < yi;
@@ -135,7 +75,7 @@ __global__ __launch_bounds__(kFkThreads) void bt_flowtop_begin(FlowtopArgs a) {
     const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < kTopDigits * kTopBins; i += kFkThreads) a.hist[i] = 0u;
     if (tid == 0) {
-        const bool ok = hdr_ok(a);
+        const bool ok = hdr_ok(a, a.slots);
         const uint32_t nf = ok ? a.hdr->n_flows : 0u, n_top = a.k < nf ? a.k : nf;
         *a.ctl = FtopCtl{ok ? 1u : 0u, nf, n_top, n_top, 0u, 0u, 0ull, 0ull};
     }
@@ -167,7 +107,7 @@ __global__ __launch_bounds__(kFkThreads) void bt_flowtop_value(FlowtopArgs a) {
             hist_add(h, on, (uint32_t)(v[u] >> 56));
         }
     }
-    const uint64_t tot = block_sum64<kFkWaves>(sum, sh);   // its barriers also close the histogram
+    const uint64_t tot = block_sum64<kFkThreads>(sum, sh);   // its barriers also close the histogram
     if (tid == 0 && tot) atomicAdd(reinterpret_cast<unsigned long long*>(&a.ctl->total), (unsigned long long)tot);
     hist_flush(h, a.hist);
 }
@@ -207,7 +147,7 @@ __global__ __launch_bounds__(kFkThreads) void bt_flowtop_pick(FlowtopArgs a, uin
     const uint64_t prefix = a.ctl->prefix;
     const uint32_t c = a.hist[p * kTopBins + bin];
     uint32_t total = 0;
-    const uint32_t excl = block_excl<kFkWaves>(c, sh, &total);   // flows in the bins above this one; its barrier follows the reads
+    const uint32_t excl = block_excl<kFkThreads>(c, sh, &total);   // flows in the bins above this one; its barrier follows the reads
     if (excl < need && need - excl <= c) {   // one thread: 1 <= need <= the flows that match the prefix
         a.ctl->prefix = prefix << 8 | bin;
         a.ctl->need = need - excl;
@@ -248,8 +188,8 @@ __global__ __launch_bounds__(kTopSortThreads) void bt_flowtop_scan(FlowtopArgs a
     uint32_t sg = 0, se = 0;
     for (uint32_t q = lo; q < hi; ++q) { sg += a.parts[q].ngt; se += a.parts[q].neq; }
     uint32_t total = 0;
-    uint32_t rg = block_excl<kSortWaves>(sg, sh, &total);
-    uint32_t re = block_excl<kSortWaves>(se, sh, &total);
+    uint32_t rg = block_excl<kTopSortThreads>(sg, sh, &total);
+    uint32_t re = block_excl<kTopSortThreads>(se, sh, &total);
     for (uint32_t q = lo; q < hi; ++q) {
         a.parts[q].rel_gt = rg; a.parts[q].rel_eq = re;
         rg += a.parts[q].ngt; re += a.parts[q].neq;
@@ -332,7 +272,7 @@ __global__ __launch_bounds__(kTopSortThreads) void bt_flowtop_sort(FlowtopArgs a
             if (a.top_tcp) tcp_copy(a.top_tcp + r, a.tcp + id);
         }
     }
-    const uint64_t top_total = block_sum64<kSortWaves>(sum, sh);
+    const uint64_t top_total = block_sum64<kTopSortThreads>(sum, sh);
     if (tid == 0) {
         bt_flow_top_result r{};
         r.n_flows = a.ctl->n_flows; r.n_top = n_top; r.metric = a.metric;

@@ -44,9 +44,9 @@
 // empty when it was claimed and slots are only emptied all at once (expire). The slot words are
 // private to the state. Across the XCDs' L2s: the kernels read only atomics' results and data
 // written by earlier kernels.
-#include "bt_dev_util.h"
+#include "bt_flowtrack_dev.h"
 #include "bt_hip_launch.h"
-#include "bt_flowtrack.h"
+#include "bt_wave.h"
 
 namespace bt {
 
@@ -54,13 +54,6 @@ namespace {
 
 constexpr uint32_t kJoinWaves = kFkJoinThreads / 64u;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-template <class A>
-__device__ __forceinline__ bool hdr_ok(const A& a) {   // the state is the tracker the host took the call for
-    const bt_flow_track_hdr* const h = a.hdr;
-    return h->magic == BT_FLOW_TRACK_MAGIC && h->flags == a.flags && h->flow_cap == a.flow_cap && h->slots == a.slots &&
-           h->n_flows <= a.flow_cap;
-}
 
 // The first 40 bytes of a bt_flow_rec or a bt_flow_track_rec (8-byte aligned): key, class, zeros.
 __device__ __forceinline__ void head_load(const void* p, uint32_t (&w)[10]) {
@@ -71,45 +64,6 @@ __device__ __forceinline__ void head_load(const void* p, uint32_t (&w)[10]) {
         w[2 * j] = (uint32_t)x;
         w[2 * j + 1] = (uint32_t)(x >> 32);
     }
-}
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1)
-        v += ((uint64_t)__shfl_xor((uint32_t)(v >> 32), o) << 32) | __shfl_xor((uint32_t)v, o);
-    return v;
-}
-
-// The exclusive scan of v over a block of kFkJoinThreads threads, and the sum in *total; sh: kJoinWaves words.
-__device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* sh, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    uint32_t incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o);
-        if (lane >= (uint32_t)o) incl += y;
-    }
-    if (lane == 63u) sh[wid] = incl;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kJoinWaves; ++w) {
-        const uint32_t x = sh[w];
-        pre += w < wid ? x : 0u;
-        tot += x;
-    }
-    __syncthreads();
-    *total = tot;
-    return pre + incl - v;
-}
-
-__device__ __forceinline__ uint64_t block_sum64(uint64_t v, uint64_t* sh) {   // ... the sum of v, to every thread
-    v = wave_sum64(v);
-    if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint64_t tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kJoinWaves; ++w) tot += sh[w];
-    __syncthreads();
-    return tot;
 }
 
 // Flow g takes the first empty slot on the probe sequence of `hash`. A slot changes once, from
@@ -125,13 +79,6 @@ __device__ __forceinline__ void claim(uint32_t* slot, uint32_t slots, uint32_t h
     }
 }
 
-__device__ __forceinline__ void rec_copy(bt_flow_track_rec* dst, const bt_flow_track_rec* src) {   // 104 B = 13 words
-    const uint64_t* const q = reinterpret_cast<const uint64_t*>(src);
-    uint64_t* const o = reinterpret_cast<uint64_t*>(dst);
-#pragma unroll
-    for (int j = 0; j < 13; ++j) o[j] = q[j];
-}
-
 }  // namespace
 
 // The header, zero records and empty slots: the whole state, grid-stride.
@@ -145,16 +92,14 @@ __global__ __launch_bounds__(kFkThreads) void bt_flowtrack_init(FlowexpArgs a) {
     uint64_t* const r = reinterpret_cast<uint64_t*>(a.recs);
     const uint64_t nr = (uint64_t)a.flow_cap * (sizeof(bt_flow_track_rec) / 8u);
     for (uint64_t x = t; x < nr; x += step) r[x] = 0ull;
-    u32x4* const q = reinterpret_cast<u32x4*>(a.slot);   // slots is a multiple of 128
-    const uint64_t nq = a.slots / 4u;
-    for (uint64_t x = t; x < nq; x += step) q[x] = u32x4{kFkEmpty, kFkEmpty, kFkEmpty, kFkEmpty};
+    slots_fill<kFkThreads>(a.slot, a.slots, kFkEmpty);
 }
 
 // U1: is the batch's flow j in the table?
 __global__ __launch_bounds__(kFkThreads) void bt_flowtrack_find(FlowtrackArgs a) {
     __shared__ uint32_t wn[kFkWaves];
     __shared__ uint64_t wp[kFkWaves], wb[kFkWaves];
-    if (!hdr_ok(a)) return;
+    if (!hdr_ok(a, a.slots)) return;
     const uint32_t have = a.ftres->n_flows, nb = have < a.n ? have : a.n;   // written by bt_flowtab_join
     const uint32_t j0 = blockIdx.x * kFkThreads;
     if (j0 >= nb) return;
@@ -212,7 +157,7 @@ __global__ __launch_bounds__(kFkJoinThreads) void bt_flowtrack_join(FlowtrackArg
     __shared__ uint64_t sh64[kJoinWaves];
     __shared__ uint32_t cut[2];   // the block the room ends in, and where its new flows start
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-    if (!hdr_ok(a)) {   // not this tracker's state: nothing is done
+    if (!hdr_ok(a, a.slots)) {   // not this tracker's state: nothing is done
         if (tid == 0) {
             if (!a.empty) *a.ctl = FkCtl{0u, 0u, 0u, 0u};
             bt_flow_track_result r{};
@@ -228,7 +173,7 @@ __global__ __launch_bounds__(kFkJoinThreads) void bt_flowtrack_join(FlowtrackArg
     uint32_t sum = 0;
     for (uint32_t p = lo; p < hi; ++p) sum += a.parts[p].nnew;
     uint32_t total = 0;
-    const uint32_t excl = block_excl(sum, sh, &total);
+    const uint32_t excl = block_excl<kFkJoinThreads>(sum, sh, &total);
     const uint32_t base = a.hdr->n_flows, room = a.flow_cap - base;
     if (tid == 0) cut[0] = kNone;
     __syncthreads();
@@ -256,8 +201,8 @@ __global__ __launch_bounds__(kFkJoinThreads) void bt_flowtrack_join(FlowtrackArg
             ob += q[7] + q[8];
         }
     }
-    op = block_sum64(op, sh64);
-    ob = block_sum64(ob, sh64);
+    op = block_sum64<kFkJoinThreads>(op, sh64);
+    ob = block_sum64<kFkJoinThreads>(ob, sh64);
     if (tid == 0) {
         bt_flow_track_hdr* const h = a.hdr;
         const uint32_t newf = total < room ? total : room, seq = h->seq;
@@ -348,7 +293,7 @@ __global__ __launch_bounds__(kFkThreads) void bt_flowtrack_ids(FlowtrackArgs a) 
 // X1: which flows are idle, as counts.
 __global__ __launch_bounds__(kFkThreads) void bt_flowexpire_mark(FlowexpArgs a) {
     __shared__ uint32_t wn[kFkWaves];
-    if (!hdr_ok(a)) return;
+    if (!hdr_ok(a, a.slots)) return;
     const uint32_t nf = a.hdr->n_flows, f0 = blockIdx.x * kFkThreads;
     if (f0 >= nf) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6, f = f0 + tid;
@@ -368,7 +313,7 @@ __global__ __launch_bounds__(kFkThreads) void bt_flowexpire_mark(FlowexpArgs a) 
 __global__ __launch_bounds__(kFkJoinThreads) void bt_flowexpire_scan(FlowexpArgs a) {
     __shared__ uint32_t sh[kJoinWaves];
     const uint32_t tid = threadIdx.x;
-    if (!hdr_ok(a)) {
+    if (!hdr_ok(a, a.slots)) {
         if (tid == 0) {
             *a.ctl = FxCtl{0u, 0u, 0u, 0u};
             bt_flow_track_expire_result r{};
@@ -383,7 +328,7 @@ __global__ __launch_bounds__(kFkJoinThreads) void bt_flowexpire_scan(FlowexpArgs
     uint32_t sum = 0;
     for (uint32_t p = lo; p < hi; ++p) sum += a.parts[p].nidle;
     uint32_t total = 0;
-    uint32_t run = block_excl(sum, sh, &total);
+    uint32_t run = block_excl<kFkJoinThreads>(sum, sh, &total);
     for (uint32_t p = lo; p < hi; ++p) {
         a.parts[p].rel = run;
         run += a.parts[p].nidle;
@@ -426,9 +371,7 @@ __global__ __launch_bounds__(kFkThreads) void bt_flowexpire_back(FlowexpArgs a) 
     const FxCtl ctl = *a.ctl;
     if (!ctl.ok || !ctl.limit) return;
     const uint64_t t = (uint64_t)blockIdx.x * kFkThreads + threadIdx.x, step = (uint64_t)gridDim.x * kFkThreads;
-    u32x4* const q = reinterpret_cast<u32x4*>(a.slot);
-    const uint64_t nq = a.slots / 4u;
-    for (uint64_t x = t; x < nq; x += step) q[x] = u32x4{kFkEmpty, kFkEmpty, kFkEmpty, kFkEmpty};
+    slots_fill<kFkThreads>(a.slot, a.slots, kFkEmpty);
     for (uint64_t f = t; f < ctl.n_before; f += step) {   // n_before <= flow_cap
         if (f < ctl.n_live) {
             rec_copy(a.recs + f, a.tmp + f);
@@ -458,13 +401,6 @@ __global__ __launch_bounds__(kFkThreads) void bt_flowexpire_claim(FlowexpArgs a)
 // _claim run as they are.
 namespace {
 
-__device__ __forceinline__ void tcp_copy(bt_flow_tcp_rec* dst, const bt_flow_tcp_rec* src) {   // 16 B, 4-byte aligned
-    const uint32_t* const q = reinterpret_cast<const uint32_t*>(src);
-    uint32_t* const o = reinterpret_cast<uint32_t*>(dst);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = q[j];
-}
-
 __device__ __forceinline__ bool tcp_leaves(const FlowexpTcpArgs& a, uint32_t f) {   // f < n_flows <= flow_cap
     return fk_tcp_leaves(a.recs[f].last_ts, a.tcp[f], a.flags, a.now, a.idle, a.closed_idle);
 }
@@ -474,7 +410,7 @@ __device__ __forceinline__ bool tcp_leaves(const FlowexpTcpArgs& a, uint32_t f) 
 // X1t: which flows leave, as counts.
 __global__ __launch_bounds__(kFkThreads) void bt_flowexpire_tcp_mark(FlowexpTcpArgs a) {
     __shared__ uint32_t wn[kFkWaves];
-    if (!hdr_ok(a)) return;
+    if (!hdr_ok(a, a.slots)) return;
     const uint32_t nf = a.hdr->n_flows, f0 = blockIdx.x * kFkThreads;
     if (f0 >= nf) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6, f = f0 + tid;
@@ -522,9 +458,7 @@ __global__ __launch_bounds__(kFkThreads) void bt_flowexpire_tcp_back(FlowexpTcpA
     const FxCtl ctl = *a.ctl;
     if (!ctl.ok || !ctl.limit) return;
     const uint64_t t = (uint64_t)blockIdx.x * kFkThreads + threadIdx.x, step = (uint64_t)gridDim.x * kFkThreads;
-    u32x4* const q = reinterpret_cast<u32x4*>(a.slot);
-    const uint64_t nq = a.slots / 4u;
-    for (uint64_t x = t; x < nq; x += step) q[x] = u32x4{kFkEmpty, kFkEmpty, kFkEmpty, kFkEmpty};
+    slots_fill<kFkThreads>(a.slot, a.slots, kFkEmpty);
     for (uint64_t f = t; f < ctl.n_before; f += step) {   // n_before <= flow_cap
         uint32_t* const s = reinterpret_cast<uint32_t*>(a.tcp + f);
         if (f < ctl.n_live) {

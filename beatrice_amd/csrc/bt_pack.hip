@@ -22,7 +22,7 @@
 //                 byte by byte (the neighbouring tile's wave writes the other bytes).
 // Every source byte is read under `0 <= offset < bytes` (zeros otherwise); every store is to
 // a byte of a record whose whole slot ends at or below cap.
-#include "bt_dev_util.h"
+#include "bt_wave.h"
 #include "bt_hip_launch.h"
 #include "bt_pack.h"
 
@@ -31,11 +31,6 @@ namespace bt {
 namespace {
 
 typedef u32x4 u32x4_any __attribute__((aligned(1)));   // a 16-B load at any byte alignment
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // The select word of tile t with the bits at or above n cleared.
 __device__ __forceinline__ uint64_t select_word(const PackArgs& a, uint32_t t) {

@@ -23,27 +23,13 @@
 //                    and *out is written or added to.
 // Lanes at or past n never load: no descriptor at or past n and no record tile at or past
 // ceil(n / 64) is read.
-#include "bt_dev_util.h"
+#include "bt_wave.h"
 #include "bt_hip_launch.h"
 #include "bt_tally.h"
 
 namespace bt {
 
 namespace {
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1)
-        v += ((uint64_t)__shfl_xor((uint32_t)(v >> 32), o) << 32) | __shfl_xor((uint32_t)v, o);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t y = __shfl_xor(v, o);
-        v = y < v ? y : v;
-    }
-    return v;
-}
 
 // Packet i (< a.n): its frame's length as the pack takes it (a fixed stride: min(stride, 65535)).
 __device__ __forceinline__ uint32_t length_of(const TallyArgs& a, uint32_t i) {
