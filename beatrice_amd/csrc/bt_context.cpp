@@ -314,6 +314,10 @@ int bt_stream_destroy(bt_ctx* c, void* stream) {
     if (!c || !stream) return set_error(BT_E_INVALID_ARGUMENT, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        bt::forget_stream(c, reinterpret_cast<hipStream_t>(stream));
+    }
     HIP_TRY(hipStreamDestroy(reinterpret_cast<hipStream_t>(stream)));
     return BT_OK;
 }

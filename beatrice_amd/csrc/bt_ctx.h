@@ -127,6 +127,19 @@ struct bt_ctx {
         int md_next = 0;
         hipStream_t cstream = nullptr;     // pipelined compaction (bt_parse_filter_device_async)
     } ws;
+    // The dynamic tail's counters (bt_tail_split.h; bt_launch.cpp tail_heads_for): one block of
+    // kTailWords words per stream that launched a late-issue main kernel. Launches on one stream
+    // never overlap, launches on two streams (a caller's own; the two output sets of the async
+    // call share the main stream) never share a block. bt_stream_destroy drops its stream's
+    // entry; a stream destroyed behind the context's back keeps it, and a later stream that gets
+    // the same handle inherits idle counters (a handle is not reused while its work is pending).
+    struct TailHeads {
+        hipStream_t stream = nullptr;
+        uint32_t* dev = nullptr;
+        uint32_t launches = 0;   // launches that claimed from it: the next one's set is launches & 1
+    };
+    static constexpr size_t kTailStreams = 64;   // beyond that a new stream's launches deal statically
+    std::vector<TailHeads> tail;
     const void* last_base = nullptr;   // host_resident's one-entry cache
     bool last_base_host = false;
 
@@ -207,6 +220,7 @@ namespace bt {
 void release_host_pipe(bt_ctx* c);       // bt_host_batch.cpp
 void release_timing_graph(bt_ctx* c);    // bt_timing.cpp
 void release_workspace(bt_ctx* c);       // bt_launch.cpp
+void forget_stream(bt_ctx* c, hipStream_t st);   // bt_launch.cpp
 void release_dfa_pools(bt_ctx* c);       // bt_program.cpp
 void release_timing(bt_ctx* c);          // bt_timing.cpp
 void release_extract_stage(bt_ctx* c);   // bt_extract_host.cpp

@@ -51,6 +51,14 @@ struct MainArgs : FrameSrc {   // bytes = read_limit
     uint32_t lean_lo;          // ... and the first of them it needs: round A skips the 16-B chunks
                                // that end at or before it (0; 12 for lean calls: nothing in a
                                // filter-only call reads the MAC addresses)
+    uint32_t* tail_heads;      // the dynamic tail's counters (bt_tail_split.h: kTailWords words, two sets
+                               // of heads; no two launches that can overlap share them); null: every
+                               // tile is dealt statically
+    uint32_t tail_set;         // the set of heads this launch claims from (0 / 1; it zeroes the other)
+    uint32_t tail_static;      // set by the launch (launch_variant): tiles dealt cyclically,
+    uint32_t tail_claim;       // tiles per ticket,
+    uint32_t tail_visits;      // heads a wave tries before it leaves, from its own on,
+    uint32_t tail_stride;      // and words between two heads (A/B: BT_TAIL)
 };
 // Frames read over PCIe (registered host memory) by a filter-only call: round A reads only
 // the 16-B chunks holding bytes 12..37 of a frame (every filter gate and the detector column)
@@ -76,6 +84,9 @@ enum RecLayout { kRecNone = 0, kRecPlanes = 1, kRecAoS = 2, kRecTiled = 3 };
 int launch_main(const MainArgs& a, const DevProgram& prog, int rec_layout, bool filter,
                 int grid_blocks, bool prefetch, void* stream, void* timing_start = nullptr,
                 void* timing_stop = nullptr);
+// Whether launch_main's kernel for this call deals a dynamic tail when a.tail_heads is set (the
+// late-issue fixed-stride kernel, cyclic order): only such a call takes a set of counters.
+bool main_deals_tail(const MainArgs& a, int rec_layout, bool filter);
 // The ordered compaction of an n-packet batch: pass_idx = the indices of the set verdict
 // bits, ascending; n_pass = their count. chunk_sums: ceil(ceil(n / 64) / kChunkTiles) words
 // of workspace.

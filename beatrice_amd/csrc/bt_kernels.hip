@@ -25,6 +25,7 @@
 // Replaces the per-packet work of reference src/parser/ProtocolParser.cpp:238-433 and
 // src/PacketFilter.cpp:57-372 (see DESIGN.md for the line-by-line mapping).
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -33,6 +34,7 @@
 #include "bt_hip_launch.h"
 #include "bt_payload_walk.h"
 #include "bt_slot_eval.h"
+#include "bt_tail_split.h"
 
 namespace bt {
 
@@ -664,7 +666,8 @@ __device__ __forceinline__ TileRange tile_range(const MainArgs& a, uint32_t wid)
         const uint32_t per = (a.ntiles + total_waves - 1) / total_waves;
         return {gw * per, min(a.ntiles, gw * per + per), 1u};
     }
-    return {gw, a.ntiles, total_waves};
+    // with a dynamic tail (bt_parse_filter_main, late issue) only the tiles below a.tail_static
+    return {gw, a.tail_heads ? a.tail_static : a.ntiles, total_waves};
 }
 
 // Tile t's decision bytes and verdict word as two unconditional buffer stores, so that a wait
@@ -717,8 +720,72 @@ void bt_parse_filter_main(MainArgs a, DevProgram prog) {
     // parse-only (nothing to overlap: C2 0.321 against 0.319 ms). Its header loads are
     // always non-temporal (BT_OPT_CACHE_DEFAULT keeps the default policy for the rest).
     constexpr bool LATE = late_issue(FIXED_LOG2, REC, FILTER);
-    if ((PREFETCH || LATE) && t < t_end) issue_loads<FIXED_LOG2, LATE>(a, t, lane, st, wide, need_max);
-    if (LATE && t < t_end) {
+    // The dynamic tail (LATE only; bt_tail_split.h): tile_range dealt the tiles below
+    // a.tail_static, the rest go by tickets. All of this state is wave-uniform.
+    const bool dyn = LATE && a.tail_heads != nullptr && !a.blocked;
+    const TailSplit split = {a.tail_static, a.tail_claim};
+    const TailShape shape = tail_shape(a.ntiles, split);
+    uint32_t head = blockIdx.x & (kTailHeads - 1u);   // the head in use, from the block's XCD label on
+    // heads the wave may still try: a head is emptied by the blocks of its own label, which
+    // leave it only once a claim there misses, so with a block of every label a wave need not
+    // try them all; a smaller grid tries every head
+    uint32_t heads_left = gridDim.x >= kTailHeads ? a.tail_visits : kTailHeads;
+    uint32_t lim = t_end, stride = step;              // the wave's tiles in hand: t, t + stride, ... < lim
+    uint32_t next_unit = kNoTile;                     // a ticket taken ahead, already read
+    uint32_t ahead = 0u;                              // lane 0: the ticket of the claim in flight
+    bool ahead_out = false;
+    // One returning atomic add on the head in use, by lane 0.
+    auto take = [&]() -> uint32_t {
+        uint32_t k = 0u;
+        if (lane == 0)
+            k = __hip_atomic_fetch_add(a.tail_heads + (a.tail_set * kTailHeads + head) * a.tail_stride, 1u, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+        return k;
+    };
+    // The ticket a claim returned: its unit, or the head is empty and the wave moves to the next.
+    auto read = [&](uint32_t k) -> uint32_t {
+        const uint32_t u = ticket_unit(shape, head, __builtin_amdgcn_readfirstlane(k));
+        if (u == kNoTile) { head = (head + 1u) & (kTailHeads - 1u); --heads_left; }
+        return u;
+    };
+    // The wave's next tile, called once per tile where the next tile's loads are issued: the next
+    // of the tiles in hand, else the first of the unit claimed ahead, else of a unit claimed now
+    // (the wave waits for it: its first claim when it had one static tile or none, and after a
+    // head ran empty); kNoTile once all heads are empty. When the tile it returns is the last in
+    // hand, the next claim goes out before that tile's loads, so the loop top's wait for those
+    // loads covers it and read() after that wait costs nothing more.
+    auto next_tile = [&](uint32_t cur) -> uint32_t {
+        uint32_t tn = cur + stride;
+        if (cur == kNoTile || tn >= lim) {
+            if (!dyn) return kNoTile;
+            uint32_t u = next_unit;
+            next_unit = kNoTile;
+            while (u == kNoTile && heads_left) u = read(take());
+            if (u == kNoTile) return kNoTile;
+            tn = unit_first(split, u);
+            stride = shape.units;
+            lim = unit_limit(a.ntiles, split, shape, u);
+        }
+        if (dyn && tn + stride >= lim && heads_left) {
+            ahead = take();
+            ahead_out = true;
+        }
+        return tn;
+    };
+    auto after_wait = [&]() {
+        if (dyn && ahead_out) {
+            next_unit = read(ahead);
+            ahead_out = false;
+        }
+    };
+    // the other set, which the stream's previous launch left and its next one claims from
+    if (dyn && blockIdx.x == 0 && wid == 0 && lane < kTailHeads)
+        __hip_atomic_store(a.tail_heads + ((a.tail_set ^ 1u) * kTailHeads + lane) * a.tail_stride, 0u, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    if (dyn && t >= t_end) t = next_tile(kNoTile);   // no static tile: the first one by ticket
+    const bool any = dyn ? t != kNoTile : t < t_end;
+    if ((PREFETCH || LATE) && any) issue_loads<FIXED_LOG2, LATE>(a, t, lane, st, wide, need_max);
+    if (LATE && any) {
         // stand-ins for a tile's decision / verdict stores (an empty range: dropped), so
         // the loop top's wait counts the same operations on the first iteration as later
         const auto r = rsrc_of(g_zero16, 0u);
@@ -726,7 +793,9 @@ void bt_parse_filter_main(MainArgs a, DevProgram prog) {
         const u32x2 z = {0u, 0u};
         __builtin_amdgcn_raw_buffer_store_b64(z, r, 16, 0, 0);
     }
-    for (; t < t_end; t += step) {
+    // One tile. `waited` runs once the tile's loads have landed, `next` names the tile whose loads
+    // a late-issue kernel sends off after this tile's record stores (kNoTile: none).
+    auto tile = [&](const uint32_t t, auto&& waited, auto&& next) __attribute__((always_inline)) {
         const uint32_t p0 = t * 64u;
         const uint32_t my = p0 + lane;
         const bool live = my < a.n;
@@ -734,6 +803,7 @@ void bt_parse_filter_main(MainArgs a, DevProgram prog) {
         // ---- 1. LOAD (this tile's windows -> LDS; next tile's loads go in flight) ----
         if (!PREFETCH && !LATE) issue_loads<FIXED_LOG2>(a, t, lane, st, wide, need_max);
         stage_to_lds<FIXED_LOG2>(st, img, lane);
+        waited();
         const uint64_t my_off = st.off;
         const uint32_t my_len = st.len;
         uint64_t qa0[FIXED_LOG2 >= 0 ? 1 : 4];
@@ -806,7 +876,10 @@ void bt_parse_filter_main(MainArgs a, DevProgram prog) {
             }
         }
 
-        if (LATE && t + step < t_end) issue_loads<FIXED_LOG2, LATE>(a, t + step, lane, st, wide, need_max);
+        if constexpr (LATE) {
+            const uint32_t tn = next();
+            if (tn != kNoTile) issue_loads<FIXED_LOG2, LATE>(a, tn, lane, st, wide, need_max);
+        }
         // ---- 3. FILTER ------------------------------------------------------
         if (FILTER) {
             uint32_t slot;
@@ -847,6 +920,24 @@ void bt_parse_filter_main(MainArgs a, DevProgram prog) {
             }
         }
         wave_lds_sync();   // the next tile overwrites this wave's image
+    };
+    // The static deal: with a dynamic tail all but the wave's last two static tiles, so that the
+    // first claim goes out a tile ahead like every later one. This loop issues the same memory
+    // operations on every path (no atomic): its loop-top wait stays a counted vmcnt.
+    const uint32_t s_end = !dyn ? t_end : t_end > 2u * step ? t_end - 2u * step : 0u;
+    if (!dyn || lim == t_end)   // (a wave whose first tile came by ticket has no static tile)
+        for (; t < s_end; t += step)
+            tile(t, [] {}, [&] { return t + step < t_end ? t + step : kNoTile; });
+    if constexpr (LATE) {
+        if (dyn) {
+            // The tail: a second instance of the tile, its next tile from next_tile(). No wave
+            // waits for another: a wave that finds every head empty leaves.
+            while (t != kNoTile) {
+                uint32_t tn = kNoTile;
+                tile(t, after_wait, [&] { return tn = next_tile(t); });
+                t = tn;
+            }
+        }
     }
 }
 
@@ -1164,7 +1255,29 @@ bool use_pipe() {
 // One launch of the variant `Kernel`: `grid` blocks when the caller fixed it (> 0); else
 // `auto_grid` blocks or, when that is 0, one residency wave of the variant, at most `cap_per_cu`
 // blocks per CU (0: no cap). Never more blocks than the batch has tiles for.
-template <auto Kernel>
+// The dynamic tail's shape (bt_tail_split.h). BT_TAIL="rounds,claim,visits,stride" in the
+// environment overrides the adopted values (A/B; rounds 0: the static deal alone).
+struct TailKnob {
+    uint32_t rounds, claim, visits, stride;
+};
+const TailKnob& tail_knob() {
+    static const TailKnob k = [] {
+        TailKnob v{kTailRounds, kTailClaim, kTailVisits, kTailStride};
+        if (const char* e = getenv("BT_TAIL")) {
+            unsigned r = 0, c = 0, h = 0, s = 0;
+            const int got = sscanf(e, "%u,%u,%u,%u", &r, &c, &h, &s);
+            if (got >= 1) v.rounds = r;
+            if (got >= 2 && c) v.claim = c;
+            if (got >= 3 && h >= 1 && h <= kTailHeads) v.visits = h;
+            if (got >= 4 && s >= 1 && s <= kTailStride) v.stride = s;
+        }
+        return v;
+    }();
+    return k;
+}
+
+// TAIL: the kernel deals a dynamic tail when the call brought counters (a.tail_heads).
+template <auto Kernel, bool TAIL = false>
 void launch_variant(const MainArgs& a, const DevProgram& prog, int grid, int auto_grid, int cap_per_cu, uint32_t dyn,
                     hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
     const uint32_t needed = (a.ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -1174,7 +1287,16 @@ void launch_variant(const MainArgs& a, const DevProgram& prog, int grid, int aut
         if (cap_per_cu) g = std::min(g, cap_per_cu * cu_count());
     }
     if ((uint32_t)g > needed) g = (int)(needed ? needed : 1);
-    launch(Kernel, dim3(g), dim3(kBlock), dyn, st, e0, e1, a, prog);
+    MainArgs b = a;
+    if (!TAIL || a.blocked || tail_knob().rounds == 0u) b.tail_heads = nullptr;
+    if (b.tail_heads) {
+        const TailSplit s = tail_split(a.ntiles, (uint32_t)g * kWavesPerBlock, tail_knob().rounds, tail_knob().claim);
+        b.tail_static = s.n_static;
+        b.tail_claim = s.claim;
+        b.tail_visits = tail_knob().visits;
+        b.tail_stride = tail_knob().stride;
+    }
+    launch(Kernel, dim3(g), dim3(kBlock), dyn, st, e0, e1, b, prog);
 }
 
 template <int FL, int REC, int F>
@@ -1231,7 +1353,7 @@ void launch_t(const MainArgs& a, const DevProgram& prog, int grid, bool pf, hipS
     // With the late issue (bt_parse_filter_main) the filter no longer needs the third
     // block: c2f 0.327 ms at 2 blocks/CU against 0.343-0.350 at 3 without it.
     constexpr int cap = FL < 0 ? 0 : F && !late_issue(FL, REC, F) ? 3 : 2;
-    launch_variant<bt_parse_filter_main<FL, REC, F, false>>(a, prog, grid, 0, cap, dyn, st, e0, e1);
+    launch_variant<bt_parse_filter_main<FL, REC, F, false>, late_issue(FL, REC, F)>(a, prog, grid, 0, cap, dyn, st, e0, e1);
 }
 
 template <int FL>
@@ -1252,6 +1374,11 @@ void launch_fl(const MainArgs& a, const DevProgram& prog, int rec, int f, int gr
 }
 
 }  // namespace
+
+bool main_deals_tail(const MainArgs& a, int rec_layout, bool filter) {
+    const bool fixed = !a.desc && (a.stride == 16 || a.stride == 32 || a.stride == 64 || a.stride == 128);
+    return fixed && filter && !a.dfa_bytes && rec_layout != kRecAoS && !a.blocked && tail_knob().rounds != 0u;
+}
 
 int launch_main(const MainArgs& a, const DevProgram& prog, int rec_layout, bool filter, int grid_blocks,
                 bool prefetch, void* stream, void* timing_start, void* timing_stop) {

@@ -9,6 +9,7 @@
 #include "bt_ctx.h"
 #include "bt_hip_util.h"
 #include "bt_resume_host.h"
+#include "bt_tail_split.h"
 
 using namespace bt;
 
@@ -29,6 +30,31 @@ void free_ws(bt_ctx* c) {
         w.chunk_sums = nullptr; w.verdict = nullptr; w.last = nullptr; w.lazy = false;
     }
     c->ws.cap = 0;
+}
+
+// The dynamic tail's counters of the main-kernel launches on `st` (bt_ctx::TailHeads), made on the
+// stream's first such launch and zeroed on st, so before that launch; from then on each launch
+// zeroes the set its successor claims from. Null, and the launch deals every tile statically,
+// while st is being captured, when the table is full, or when the allocation fails.
+bt_ctx::TailHeads* tail_heads_for(bt_ctx* c, hipStream_t st) {
+    // a captured launch replays with the set it was captured with: static deal
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    for (auto& t : c->tail)
+        if (t.stream == st) return &t;
+    if (c->tail.size() >= bt_ctx::kTailStreams) return nullptr;
+    uint32_t* d = nullptr;
+    if (hipMalloc(&d, kTailWords * sizeof(uint32_t)) != hipSuccess ||
+        hipMemsetAsync(d, 0, kTailWords * sizeof(uint32_t), st) != hipSuccess) {
+        (void)hipGetLastError();
+        if (d) (void)hipFree(d);
+        return nullptr;
+    }
+    c->tail.push_back({st, d, 0u});
+    return &c->tail.back();
 }
 
 bool ctx_stream(const bt_ctx* c, hipStream_t s) { return s == c->stream || (c->ws.cstream && s == c->ws.cstream); }
@@ -174,6 +200,7 @@ int run_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, hipStream_t st
     a.verdict = o->verdict ? o->verdict : (w ? w->verdict : nullptr);
     if (w && !o->verdict) { int rc = ws_touch(c, w, st); if (rc) return rc; }   // the main kernel writes w->verdict
     a.blocked = (c->opts.flags & BT_OPT_TILE_BLOCKED) ? 1u : 0u;
+    // fixed stride with a filter: the late-issue kernel, which deals its last tiles by ticket
     // Lean round A for frames read over PCIe, filter-only calls: the filters and the
     // detector read bytes 12..37, so round A reads only the 16-B chunks holding them (A/Bs:
     // round 3's 46-B first round against the 64-B window, profiles/r03/e2e/lean_ab.jsonl:
@@ -231,6 +258,12 @@ int run_device(bt_ctx* c, const bt_batch* b, const bt_outputs* o, hipStream_t st
         mend = c->ws.main_done[c->ws.md_next];
         c->ws.md_next = (c->ws.md_next + 1) % bt_ctx::kMainDone;
     }
+    // the late-issue kernel deals its last tiles by ticket: the stream's counters, sets alternating
+    if (main_deals_tail(a, rec, filter))
+        if (bt_ctx::TailHeads* t = tail_heads_for(c, st)) {
+            a.tail_heads = t->dev;
+            a.tail_set = t->launches++ & 1u;
+        }
     int rc = launch_main(a, c->prog, rec, filter, c->grid, !(c->opts.flags & BT_OPT_NO_PREFETCH), st, e0, mend);
     if (rc) return set_error(rc, "main kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     if (w && !o->verdict) { if ((rc = ws_done(c, w, st))) return rc; }
@@ -301,6 +334,19 @@ void release_workspace(bt_ctx* c) {
     for (auto e : c->ws.main_done)
         if (e) (void)hipEventDestroy(e);
     if (c->ws.cstream) (void)hipStreamDestroy(c->ws.cstream);
+    for (auto& t : c->tail) (void)hipFree(t.dev);
+    c->tail.clear();
+}
+
+// A caller's stream is about to be destroyed (it has been synchronized): its counters go with
+// it, so that a later stream with the same handle starts with its own.
+void forget_stream(bt_ctx* c, hipStream_t st) {
+    for (size_t i = 0; i < c->tail.size(); ++i)
+        if (c->tail[i].stream == st) {
+            (void)hipFree(c->tail[i].dev);
+            c->tail.erase(c->tail.begin() + (long)i);
+            return;
+        }
 }
 
 void release_walk_stages(bt_ctx* c) {
