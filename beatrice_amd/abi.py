@@ -518,6 +518,117 @@ def flow_track_expire_tcp_scratch_bytes(flow_cap: int) -> int:
     return b.value
 
 
+# bt_flow_stat_rec's seen bits (shifted left by 16 for direction 1)
+FSEEN_TCP, FSEEN_UDP, FSEEN_ICMP, FSEEN_ICMP6, FSEEN_OTHER = 0x01, 0x02, 0x04, 0x08, 0x10
+FSEEN_FRAGMENT, FSEEN_IP_OPTIONS, FSEEN_VLAN, FSEEN_L4 = 0x20, 0x40, 0x80, 0x100
+FSEEN_NAMES = ((FSEEN_TCP, "tcp"), (FSEEN_UDP, "udp"), (FSEEN_ICMP, "icmp"), (FSEEN_ICMP6, "icmp6"), (FSEEN_OTHER, "other"))
+
+# numpy view of bt_flow_stat_rec (128 B): record f of a side table belongs to flow number f
+FlowStatRec = np.dtype({
+    "names": ["seen", "proto_max", "payload_packets", "ttl_max", "ttl_min_c", "len_max", "len_min_c", "payload_bytes", "len_sq",
+              "syn_ts_c", "synack_ts_c", "ack_ts_c"],
+    "formats": ["<u4", "<u4", ("<u4", 2), ("<u4", 2), ("<u4", 2), ("<u4", 2), ("<u4", 2), ("<u8", 2), ("<u8", 2), ("<u8", 2),
+                ("<u8", 2), ("<u8", 2)],
+    "offsets": [0, 4, 8, 16, 24, 32, 40, 48, 64, 80, 96, 112],
+    "itemsize": 128,
+})
+
+
+class FlowStatResult(_Counts):
+    """bt_flow_stat_result (32 B): the counts of a statistics side table update."""
+    _fields_ = [("n", ctypes.c_uint32), ("ip_packets", ctypes.c_uint32), ("l4_packets", ctypes.c_uint32),
+                ("tcp_packets", ctypes.c_uint32), ("bad_ids", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class FlowStatRttOut(_Counts):
+    """bt_flow_stat_rtt_out (32 B)."""
+    _fields_ = [("has_initiator", ctypes.c_uint32), ("initiator", ctypes.c_uint32), ("server_valid", ctypes.c_uint32),
+                ("client_valid", ctypes.c_uint32), ("rtt_server", ctypes.c_uint64), ("rtt_client", ctypes.c_uint64)]
+
+
+class FlowSideMove(ctypes.Structure):
+    """bt_flow_side_move (48 B): a side table, where expired side records go, the expire's remap and result."""
+    _fields_ = [("side", ctypes.c_void_p), ("expired_side", ctypes.c_void_p), ("remap", ctypes.c_void_p), ("result", ctypes.c_void_p),
+                ("rec_bytes", ctypes.c_uint32), ("flow_cap", ctypes.c_uint32), ("expired_cap", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+def flow_stat_update_host(data, desc, flow_id, table_flags: int, stat: np.ndarray, ts=None, batch_ts: int = 0, nbytes=None) -> dict:
+    """bt_flow_stat_update_host (host only): the frames desc (packed descriptors) lists in `data`, numbered
+    by flow_id and stamped ts[i] (or batch_ts), added to the side table `stat` (FlowStatRec, in place).
+    Returns the result dict."""
+    a = _byte_view(data)
+    keep = a if len(a) else np.zeros(1, np.uint8)
+    d = np.ascontiguousarray(desc, np.uint64)
+    n = len(d)
+    ids = np.ascontiguousarray(flow_id, np.uint32)
+    t = None if ts is None else np.ascontiguousarray(ts, np.uint64)
+    if len(ids) != n or stat.dtype != FlowStatRec or not stat.flags["C_CONTIGUOUS"] or (t is not None and len(t) != n):
+        raise ValueError("flow_stat_update_host: one flow_id (and ts) per descriptor and a contiguous FlowStatRec table")
+    res = FlowStatResult()
+    upd = FlowTrackUpdate(t.ctypes.data if t is not None and n else None, batch_ts)
+    _check(lib().bt_flow_stat_update_host(keep.ctypes.data, len(a) if nbytes is None else nbytes, d.ctypes.data if n else None, n,
+                                          ids.ctypes.data if n else None, table_flags, ctypes.byref(upd),
+                                          stat.ctypes.data if len(stat) else None, len(stat), ctypes.addressof(res)))
+    return res.as_dict()
+
+
+def flow_stat_rtt(rec) -> dict:
+    """bt_flow_stat_rtt (host only, pure): the initiator and the two handshake round-trip times of one
+    FlowStatRec, as the dict of bt_flow_stat_rtt_out."""
+    r = np.ascontiguousarray(rec, FlowStatRec).reshape(1)
+    out = FlowStatRttOut()
+    _check(lib().bt_flow_stat_rtt(r.ctypes.data, ctypes.addressof(out)))
+    return out.as_dict()
+
+
+def decode_flow_stat(rec) -> dict:
+    """One FlowStatRec in plain values: the complemented minima and stamps undone, None where nothing
+    was seen. Lists are per direction."""
+    r = np.ascontiguousarray(rec, FlowStatRec).reshape(1)[0]
+    inv32 = lambda v: None if int(v) == 0 else 0xFFFFFFFF - int(v)  # noqa: E731
+    inv64 = lambda v: None if int(v) == 0 else 0xFFFFFFFFFFFFFFFF - int(v)  # noqa: E731
+    seen = int(r["seen"])
+    return {
+        "seen": [seen & 0xFFFF, seen >> 16],
+        "protocols": [name for bit, name in FSEEN_NAMES if (seen | seen >> 16) & bit],
+        "proto_max": int(r["proto_max"]),
+        "payload_packets": [int(v) for v in r["payload_packets"]],
+        "payload_bytes": [int(v) for v in r["payload_bytes"]],
+        "ttl_max": [int(v) if int(c) else None for v, c in zip(r["ttl_max"], r["ttl_min_c"])],
+        "ttl_min": [inv32(v) for v in r["ttl_min_c"]],
+        "len_max": [int(v) if int(c) else None for v, c in zip(r["len_max"], r["len_min_c"])],
+        "len_min": [inv32(v) for v in r["len_min_c"]],
+        "len_sq": [int(v) for v in r["len_sq"]],
+        "syn_ts": [inv64(v) for v in r["syn_ts_c"]],
+        "synack_ts": [inv64(v) for v in r["synack_ts_c"]],
+        "ack_ts": [inv64(v) for v in r["ack_ts_c"]],
+    }
+
+
+def flow_track_side_move_scratch_bytes(flow_cap: int, rec_bytes: int) -> int:
+    """bt_flow_track_side_move_scratch_bytes (host only)."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_track_side_move_scratch_bytes(flow_cap, rec_bytes, ctypes.byref(b)))
+    return b.value
+
+
+def flow_track_side_move_host(side: np.ndarray, remap, result: dict, expired_cap: int | None = None):
+    """bt_flow_track_side_move_host: the side table `side` (a contiguous array of flow_cap records, in
+    place) through the expire that gave remap (flow_cap u32) and result (its dict). Returns the
+    side records of the expired flows ([min(n_expired, expired_cap)]), or None when expired_cap is None."""
+    if not side.flags["C_CONTIGUOUS"]:
+        raise ValueError("flow_track_side_move_host: a contiguous side table")
+    rm = np.ascontiguousarray(remap, np.uint32)
+    res = FlowTrackExpireResult(result["n_flows_before"], result["n_flows"], result["n_idle"], result["n_expired"], result["status"],
+                                (ctypes.c_uint32 * 3)(0, 0, 0))
+    gone = None if expired_cap is None else np.zeros(max(1, expired_cap), side.dtype)
+    m = FlowSideMove(side.ctypes.data if len(side) else None, gone.ctypes.data if gone is not None else None,
+                     rm.ctypes.data if len(rm) else None, ctypes.addressof(res), side.dtype.itemsize, len(side), expired_cap or 0, 0)
+    _check(lib().bt_flow_track_side_move_host(ctypes.byref(m)))
+    return None if gone is None else gone[:min(result["n_expired"], expired_cap)]
+
+
 # bt_flow_track_top_*: the metric a top-K query orders by, and its limit on k
 FLOW_TOP_BYTES, FLOW_TOP_PACKETS, FLOW_TOP_DURATION, FLOW_TOP_TCP_SYN, FLOW_TOP_TCP_RST = range(5)
 FLOW_TOP_MAX_K = 4096
@@ -741,6 +852,8 @@ EXPORTS = [
     "bt_time_flow_top_host",
     "bt_flow_track_hosts_scratch_bytes", "bt_flow_track_hosts_device", "bt_flow_track_hosts_host", "bt_time_flow_hosts",
     "bt_time_flow_hosts_host",
+    "bt_flow_stat_update_device", "bt_flow_stat_update_host", "bt_flow_stat_rtt", "bt_time_flow_stat",
+    "bt_flow_track_side_move_scratch_bytes", "bt_flow_track_side_move_device", "bt_flow_track_side_move_host",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -829,6 +942,13 @@ def lib() -> ctypes.CDLL:
         "bt_flow_track_hosts_host": (ctypes.c_int, [vp, u64, ctypes.POINTER(FlowHostsOpts), vp, ctypes.POINTER(FlowHostsOut)]),
         "bt_time_flow_hosts": (ctypes.c_int, [vp, vp, ctypes.POINTER(FlowHostsOpts), vp, vp, u64, ctypes.POINTER(FlowHostsOut), u32, vp]),
         "bt_time_flow_hosts_host": (ctypes.c_int, [vp, vp, u32, vp, ctypes.POINTER(FlowHostsOpts), u32, vp, vp, vp, vp]),
+        "bt_flow_stat_update_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, u32, ctypes.POINTER(FlowTrackUpdate), vp, u32, vp, vp]),
+        "bt_flow_stat_update_host": (ctypes.c_int, [vp, u64, vp, u32, vp, u32, ctypes.POINTER(FlowTrackUpdate), vp, u32, vp]),
+        "bt_flow_stat_rtt": (ctypes.c_int, [vp, vp]),
+        "bt_time_flow_stat": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, u32, ctypes.POINTER(FlowTrackUpdate), vp, u32, vp, u32, vp]),
+        "bt_flow_track_side_move_scratch_bytes": (ctypes.c_int, [u32, u32, ctypes.POINTER(u64)]),
+        "bt_flow_track_side_move_device": (ctypes.c_int, [vp, ctypes.POINTER(FlowSideMove), vp, u64, vp]),
+        "bt_flow_track_side_move_host": (ctypes.c_int, [ctypes.POINTER(FlowSideMove)]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -1246,6 +1366,36 @@ class Context:
         ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
         _check(lib().bt_flow_tcp_update_device(self.h, ctypes.byref(batch), ptr(flow_id), table_flags, ptr(tcp), flow_cap,
                                                ptr(result), stream))
+
+    def flow_stat_update(self, batch: Batch, flow_id, table_flags: int, stat, flow_cap: int, result, ts=None, batch_ts: int = 0,
+                         stream=None):
+        """bt_flow_stat_update_device: the IP packets of `batch` add protocol, TTL, length, payload and
+        handshake stamps to the side table `stat` (flow_cap FlowStatRec on the device, zeroed once by
+        the caller) at their flow number flow_id[i] (n u32 from flow_table_device or flow_track_update
+        under the same table_flags). A packet's timestamp is ts[i] (device, n u64) or batch_ts.
+        result: 32 B (FlowStatResult), 8-byte aligned. Pointers are addresses or DeviceBuffers.
+        Asynchronous on `stream`: enqueue it behind the call that wrote flow_id."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        upd = FlowTrackUpdate(ptr(ts), batch_ts)
+        _check(lib().bt_flow_stat_update_device(self.h, ctypes.byref(batch), ptr(flow_id), table_flags, ctypes.byref(upd), ptr(stat),
+                                                flow_cap, ptr(result), stream))
+
+    def flow_track_side_move(self, side, rec_bytes: int, flow_cap: int, remap, result, scratch, scratch_bytes: int,
+                             expired_side=None, expired_cap: int = 0, stream=None):
+        """bt_flow_track_side_move_device: the side table `side` (flow_cap records of rec_bytes on the
+        device) through the expire that wrote remap (flow_cap u32) and result (its 32 B, on the
+        device): survivors to their new number, zeros behind them, the expired flows' records to
+        expired_side[:expired_cap] (optional). scratch: flow_track_side_move_scratch_bytes(flow_cap,
+        rec_bytes) bytes, 256-byte aligned. Asynchronous on `stream`: enqueue it behind the expire."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        m = FlowSideMove(ptr(side), ptr(expired_side), ptr(remap), ptr(result), rec_bytes, flow_cap, expired_cap, 0)
+        _check(lib().bt_flow_track_side_move_device(self.h, ctypes.byref(m), ptr(scratch), scratch_bytes, stream))
+
+    # the host-only forms beside their device forms
+    flow_stat_update_host = staticmethod(flow_stat_update_host)
+    flow_stat_rtt = staticmethod(flow_stat_rtt)
+    flow_track_side_move_scratch_bytes = staticmethod(flow_track_side_move_scratch_bytes)
+    flow_track_side_move_host = staticmethod(flow_track_side_move_host)
 
     def flow_track_top(self, state, metric: int, k: int, scratch, scratch_bytes: int, result, top_id=None, top_value=None,
                        top=None, tcp=None, top_tcp=None, stream=None):

@@ -267,6 +267,10 @@ int run_flow_track_update(bt_ctx* c, void* state, const bt_batch* frames, const 
 int run_flow_tcp(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, uint32_t table_flags, bt_flow_tcp_rec* tcp,
                  uint32_t flow_cap, bt_flow_tcp_result* result, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 
+// bt_flowstat_host.cpp (bt_timing.cpp's bt_time_flow_stat times the same launch)
+int run_flow_stat(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, uint32_t table_flags, const bt_flow_track_update* upd,
+                  bt_flow_stat_rec* stat, uint32_t flow_cap, bt_flow_stat_result* result, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+
 // bt_flowtop_host.cpp (bt_timing.cpp's bt_time_flow_top times the same launches)
 int run_flow_track_top(bt_ctx* c, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
                        uint64_t scratch_bytes, const bt_flow_top_out* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1);

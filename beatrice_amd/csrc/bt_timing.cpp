@@ -235,6 +235,25 @@ int bt_time_flow_tcp(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id,
     return BT_OK;
 }
 
+int bt_time_flow_stat(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, uint32_t table_flags, const bt_flow_track_update* upd,
+                      bt_flow_stat_rec* stat, uint32_t flow_cap, bt_flow_stat_result* result, uint32_t iters, float* ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !frames || !frames->n || !iters || !ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int rc = run_flow_stat(c, frames, flow_id, table_flags, upd, stat, flow_cap, result, c->stream, c->timing.tev[2 * i],
+                                   c->timing.tev[2 * i + 1])) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    return BT_OK;
+}
+
 int bt_time_flow_top(bt_ctx* c, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
                      uint64_t scratch_bytes, const bt_flow_top_out* out, uint32_t iters, float* ms) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return

@@ -48,6 +48,14 @@ __device__ __forceinline__ uint64_t wave_max64(uint64_t v) {
     return v;
 }
 
+__device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t y = __shfl_xor(v, o);
+        v = y > v ? y : v;
+    }
+    return v;
+}
+
 // The exclusive scan of v over a block of Threads threads, and the sum in *total; sh: Threads / 64 words.
 template <uint32_t Threads>
 __device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* sh, uint32_t* total) {

@@ -90,7 +90,9 @@ extern "C" {
  * bt_flow_track_expire_tcp_scratch_bytes, bt_flow_track_expire_tcp_device,
  * bt_flow_track_expire_tcp_host, bt_flow_track_top_scratch_bytes, bt_flow_track_top_device,
  * bt_flow_track_top_host, bt_flow_track_hosts_scratch_bytes, bt_flow_track_hosts_device,
- * bt_flow_track_hosts_host. */
+ * bt_flow_track_hosts_host, bt_flow_stat_update_device, bt_flow_stat_update_host,
+ * bt_flow_stat_rtt, bt_flow_track_side_move_scratch_bytes, bt_flow_track_side_move_device,
+ * bt_flow_track_side_move_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -860,6 +862,105 @@ int  bt_flow_track_expire_tcp_device(bt_ctx* ctx, void* state, uint64_t now, uin
                                      void* scratch, uint64_t scratch_bytes, const bt_flow_track_expire_out* out, void* stream);
 int  bt_flow_track_expire_tcp_host(void* state, uint64_t state_bytes, uint64_t now, uint64_t idle,
                                    const bt_flow_track_expire_tcp* x, const bt_flow_track_expire_out* out);
+
+/* ---- per-flow statistics side table: protocol, sizes, TTL, payload, handshake stamps --------
+ * What kind of flow a flow is (IPFIX protocolIdentifier and friends), beside the flow records
+ * and the TCP side table. The table is flow_cap records bt_flow_stat_rec of the caller's memory,
+ * 8-byte aligned; record f belongs to flow number f of a per-batch table or of a tracker. The
+ * caller zeroes it once (all-zero = nothing seen); there is no init call.
+ * Every field is an OR, an integer sum or a maximum, so an update is exact and bit-identical from
+ * run to run however many packets are taken in parallel. Minima are stored
+ * complemented: ttl_min_c, len_min_c and the *_ts_c stamps hold ~x of the smallest x seen, so that
+ * zero reads as "none" and a minimum is a maximum of ~x. A timestamp of 2^64 - 1 therefore reads
+ * as absent.
+ * bt_flow_stat_update_device: packet i contributes when flow_id[i] < flow_cap and the walk of
+ * bt_flow_fanout_device (at most two tags, no IPv6 extension headers) finds a whole IPv4 or IPv6
+ * header in its frame. A BT_FLOW_ID_* sentinel contributes nothing; any other id >= flow_cap
+ * counts in bad_ids and contributes nothing. dir is the TCP side table's: 0 without
+ * BT_FLOWTAB_BIDIRECTIONAL, else 1 when the key the table forms under table_flags has its
+ * endpoints swapped. A contributing packet adds
+ *   seen |= bits << (16 dir), the BT_FSEEN_* bits below; proto_max = max(.., protocol / next header);
+ *   ttl_max[dir], ttl_min_c[dir] from the IPv4 TTL / IPv6 hop limit; len_max[dir], len_min_c[dir]
+ *   and len_sq[dir] += length^2 from the frame length min(len, 65535), as bytes[] of the flow record;
+ *   with a whole TCP / UDP header under the flow key's rule (BT_FSEEN_L4): payload =
+ *   max(0, ip_payload - hdr) in signed 32-bit arithmetic, ip_payload = IPv4 total_length - 4 IHL
+ *   or the IPv6 payload_length, hdr = 4 (tcp[12] >> 4) for TCP and 8 for UDP (header fields only:
+ *   captures may be snapped); payload_bytes[dir] += payload, payload_packets[dir] += payload > 0;
+ *   for such a TCP packet with flags byte fl and timestamp t (upd->ts[i], device, or with ts ==
+ *   NULL upd->batch_ts, as the tracker's update): SYN set and ACK clear: syn_ts_c[dir] = max(.., ~t);
+ *   SYN and ACK set: synack_ts_c[dir]; ACK set, SYN and RST clear: ack_ts_c[dir].
+ * Frame bytes are read under the fan-out's read rule: a byte at or past `bytes` reads as zero.
+ * Ordering, stream, n == 0 and the refusals are bt_flow_tcp_update_device's, with a null upd and
+ * a misaligned ts (8 bytes) refused too, and `stat` 8-byte aligned. Nothing is written outside
+ * stat[0 .. flow_cap) and *result.
+ * bt_flow_stat_update_host: the same on the calling thread, bit-identical (upd->ts: host memory).
+ * bt_flow_stat_rtt: host only and pure; handshake round-trip times from one record's stamps. The
+ * initiator d is the direction that has a syn stamp; with both, the earlier wins and a tie goes to
+ * 0; with neither, nothing is reported (has_initiator = 0). rtt_server = synack[1 - d] - syn[d],
+ * valid when that synack stamp exists and is >= syn[d]; rtt_client = ack[d] - synack[1 - d],
+ * valid when rtt_server is, ack[d] exists and is >= synack[1 - d]. Without
+ * BT_FLOWTAB_BIDIRECTIONAL every packet has direction 0 and the reverse direction is another
+ * flow: no RTT is ever reported there.
+ *
+ * bt_flow_track_side_move_device carries any side table (records of rec_bytes bytes, a multiple
+ * of 4 in 4 .. 256, 4-byte aligned) through an expire, by the expire's own remap. It is enqueued
+ * behind the bt_flow_track_expire_device (or _tcp_) call that wrote m->remap and *m->result and
+ * reads n_flows_before, n_flows and n_expired from *m->result on the device. For old <
+ * n_flows_before: a survivor goes to side[remap[old]]; the k-th BT_FLOW_ID_EXPIRED entry in
+ * ascending old goes to expired_side[k] when k < expired_cap (expired_side optional); entries
+ * [n_flows, n_flows_before) become zero; entries at or past n_flows_before are not touched; a
+ * remap value that is neither EXPIRED nor < n_flows writes nothing; an expire that removed nothing
+ * or reported status = 1 moves nothing. Counts above flow_cap are taken as flow_cap. Scratch:
+ * bt_flow_track_side_move_scratch_bytes(flow_cap, rec_bytes), 256-byte aligned. Refused with
+ * BT_E_INVALID_ARGUMENT before the context or any HIP call: a null m, side (with flow_cap > 0),
+ * remap (with flow_cap > 0), result or scratch; misalignment (side, expired_side, remap 4 bytes,
+ * result 8, scratch 256); rec_bytes not a multiple of 4 in 4 .. 256; expired_cap != 0 without
+ * expired_side; a non-zero reserved; scratch_bytes below the need; then a null context.
+ * bt_flow_track_side_move_host: the same on the calling thread, *m->result in host memory. */
+enum { BT_FSEEN_TCP = 0x01, BT_FSEEN_UDP = 0x02, BT_FSEEN_ICMP = 0x04 /* IPv4 and protocol 1 */,
+       BT_FSEEN_ICMP6 = 0x08 /* IPv6 and next header 58 */, BT_FSEEN_OTHER = 0x10,
+       BT_FSEEN_FRAGMENT = 0x20 /* IPv4 with flags & 0x3FFF != 0 */, BT_FSEEN_IP_OPTIONS = 0x40 /* IPv4 with IHL > 5 */,
+       BT_FSEEN_VLAN = 0x80 /* at least one tag */, BT_FSEEN_L4 = 0x100 /* a whole TCP / UDP header under the flow key's rule */ };
+
+typedef struct bt_flow_stat_rec {     /* 128 B, 8-byte aligned; all-zero = nothing seen */
+    uint32_t seen;                /* OR of BT_FSEEN_* << (16 * dir) */
+    uint32_t proto_max;           /* max of the IPv4 protocol / IPv6 next header */
+    uint32_t payload_packets[2];  /* packets with L4 payload > 0; mod 2^32 */
+    uint32_t ttl_max[2], ttl_min_c[2];   /* IPv4 TTL / IPv6 hop limit; *_c = ~minimum */
+    uint32_t len_max[2], len_min_c[2];   /* frame length min(len, 65535), as bytes[] of the flow record */
+    uint64_t payload_bytes[2];    /* L4 payload bytes from the header fields; mod 2^64 */
+    uint64_t len_sq[2];           /* sum of length^2; mod 2^64 (with packets[] and bytes[]: the variance) */
+    uint64_t syn_ts_c[2], synack_ts_c[2], ack_ts_c[2];   /* ~(earliest timestamp), per direction */
+} bt_flow_stat_rec;
+
+typedef struct bt_flow_stat_result {  /* 32 B, device-visible, 8-byte aligned */
+    uint32_t n, ip_packets, l4_packets, tcp_packets, bad_ids, reserved[3];
+} bt_flow_stat_result;
+
+typedef struct bt_flow_stat_rtt_out { /* 32 B */
+    uint32_t has_initiator, initiator;   /* initiator: 0 or 1, 0 when has_initiator == 0 */
+    uint32_t server_valid, client_valid;
+    uint64_t rtt_server, rtt_client;     /* 0 when not valid */
+} bt_flow_stat_rtt_out;
+
+typedef struct bt_flow_side_move {
+    void* side;                   /* the side table, flow_cap records of rec_bytes */
+    void* expired_side;           /* optional, expired_cap records */
+    const uint32_t* remap;        /* the expire's, flow_cap entries */
+    const bt_flow_track_expire_result* result;   /* the expire's own, device memory */
+    uint32_t rec_bytes /* multiple of 4, 4..256 */, flow_cap, expired_cap, reserved;
+} bt_flow_side_move;
+
+int  bt_flow_stat_update_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id /* device, n */,
+                                uint32_t table_flags, const bt_flow_track_update* upd, bt_flow_stat_rec* stat,
+                                uint32_t flow_cap, bt_flow_stat_result* result, void* stream);
+int  bt_flow_stat_update_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n,
+                              const uint32_t* flow_id, uint32_t table_flags, const bt_flow_track_update* upd /* ts: host */,
+                              bt_flow_stat_rec* stat, uint32_t flow_cap, bt_flow_stat_result* result);
+int  bt_flow_stat_rtt(const bt_flow_stat_rec* rec, bt_flow_stat_rtt_out* out);   /* host only, pure */
+int  bt_flow_track_side_move_scratch_bytes(uint32_t flow_cap, uint32_t rec_bytes, uint64_t* bytes);
+int  bt_flow_track_side_move_device(bt_ctx* ctx, const bt_flow_side_move* m, void* scratch, uint64_t scratch_bytes, void* stream);
+int  bt_flow_track_side_move_host(const bt_flow_side_move* m);
 
 /* ---- top-K flows of a tracker: the largest flows by a measure, selected on the device ------
  * bt_flow_track_top_device: the k largest flows of the tracker at `state` by opts->metric,

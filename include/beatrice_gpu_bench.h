@@ -124,6 +124,12 @@ int  bt_time_flow_track(bt_ctx* ctx, void* state, const bt_batch* frames, const 
  * in front of it is outside the pair). From the second call on every flag bit is already set. */
 int  bt_time_flow_tcp(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id, uint32_t table_flags,
                       bt_flow_tcp_rec* tcp, uint32_t flow_cap, bt_flow_tcp_result* result, uint32_t iters, float* ms);
+/* bt_flow_stat_update_device `iters` times on the context's stream into the same side table; ms[i] =
+ * call i's kernel, from an event pair recorded by its own dispatch (the 32-byte memset of *result
+ * in front of it is outside the pair). From the second call on every OR and maximum is already there. */
+int  bt_time_flow_stat(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id, uint32_t table_flags,
+                       const bt_flow_track_update* upd, bt_flow_stat_rec* stat, uint32_t flow_cap,
+                       bt_flow_stat_result* result, uint32_t iters, float* ms);
 /* What the tracker replaces, `iters` times: copy_ms[i] = the n_flows records of a per-batch table
  * (flows, on the device) copied to pinned host memory (wall clock, the wait included), merge_ms[i]
  * = those records merged into the host tracker state at host_state (bt_flow_track_init_host's) on

@@ -5,7 +5,7 @@ the file (the NetFlow / conntrack view of a capture).
 Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [--bidirectional] [--l3-only]
                                   [--top N] [--format csv|json] [--chunk-packets N]
                                   [--track [--idle SECONDS] [--flow-cap N] [--tcp [--closed-idle SECONDS]]
-                                           [--by bytes|packets|duration|syn|rst]
+                                           [--stats] [--by bytes|packets|duration|syn|rst]
                                            [--hosts [--top N --by bytes|packets|flows]]]
   --filter         as tools/pcap_filter.py takes it; only passing packets are counted
   --bidirectional  both directions of a conversation are one flow (BT_FLOWTAB_BIDIRECTIONAL): the
@@ -29,6 +29,16 @@ Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [-
                    (packets with SYN and no ACK, with FIN, with RST). Still one wait without --idle.
   --closed-idle SECONDS  with --tcp and --idle: a closed or reset connection ages out once its last packet is more
                    than SECONDS older than the chunk's last packet (bt_flow_track_expire_tcp_device)
+  --stats          with --track (with or without --tcp): a statistics side table beside the tracker
+                   (bt_flow_stat_update_device behind every update). Adds the columns protocols (tcp, udp, icmp, icmp6,
+                   other: every kind seen on the flow, joined by +), proto_max, and per direction (the second with the
+                   suffix _rev) len_min, len_mean, len_max, len_stddev (frame lengths; the mean and the population
+                   standard deviation from the flow record's packets and bytes and the sum of squares, three decimals),
+                   ttl_min, ttl_max, payload_bytes and payload_packets (L4 payload by the IP and TCP header fields); with
+                   --bidirectional also initiator (fwd or rev: who sent the first SYN), rtt_server (SYN to SYN-ACK) and
+                   rtt_client (SYN-ACK to ACK) in the capture's time unit (micro- or nanoseconds), empty where the
+                   handshake was not seen. With --idle the statistics of a flow that ages out leave with it
+                   (bt_flow_track_side_move_device behind the expire). Not with --top or --hosts.
   --by MEASURE     with --track and --top N, N <= 4096: what the top is ordered by, largest first and the
                    earliest-seen flow first among equals: bytes (default), packets (both directions), duration
                    (last minus first packet time by the pcap record headers), syn or rst (with --tcp: packets with
@@ -70,6 +80,9 @@ from pcap_stats import MASK48, chunks_of  # noqa: E402
 K_HOST = 9   # enum bt_filter_kind
 COLUMNS = ("class", "src", "dst", "sport", "dport", "packets", "bytes", "packets_rev", "bytes_rev", "first", "last")
 TCP_COLUMNS = ("tcp_flags_fwd", "tcp_flags_rev", "tcp_state", "syn", "fin", "rst")
+STAT_DIR_COLUMNS = ("len_min", "len_mean", "len_max", "len_stddev", "ttl_min", "ttl_max", "payload_bytes", "payload_packets")
+STAT_COLUMNS = ("protocols", "proto_max") + STAT_DIR_COLUMNS + tuple(c + "_rev" for c in STAT_DIR_COLUMNS)
+RTT_COLUMNS = ("initiator", "rtt_server", "rtt_client")
 U64_MAX = (1 << 64) - 1
 HOST_COLUMNS = ("address", "flows_src", "flows_dst", "packets_sent", "bytes_sent", "packets_received", "bytes_received",
                 "first_seen", "last_seen")
@@ -107,6 +120,25 @@ def describe_host(h, with_tcp: bool, unit: int, digits: int) -> dict:
     return r
 
 
+def describe_stats(r: dict, rec, packets, nbytes, bidirectional: bool):
+    """The --stats columns of one output line from a bt_flow_stat_rec and the flow record's packets and bytes per direction."""
+    d = abi.decode_flow_stat(rec)
+    r["protocols"], r["proto_max"] = "+".join(d["protocols"]), d["proto_max"]
+    for k, suffix in enumerate(("", "_rev")):
+        n, b, sq = packets[k], nbytes[k], d["len_sq"][k]
+        seen = d["len_min"][k] is not None
+        r["len_min" + suffix], r["len_max" + suffix] = d["len_min"][k], d["len_max"][k]
+        r["len_mean" + suffix] = f"{b / n:.3f}" if seen and n else None
+        r["len_stddev" + suffix] = f"{max(0, n * sq - b * b) ** 0.5 / n:.3f}" if seen and n else None   # exact up to the root
+        r["ttl_min" + suffix], r["ttl_max" + suffix] = d["ttl_min"][k], d["ttl_max"][k]
+        r["payload_bytes" + suffix], r["payload_packets" + suffix] = d["payload_bytes"][k], d["payload_packets"][k]
+    if bidirectional:
+        t = abi.flow_stat_rtt(rec)
+        r["initiator"] = ("fwd", "rev")[t["initiator"]] if t["has_initiator"] else None
+        r["rtt_server"] = t["rtt_server"] if t["server_valid"] else None
+        r["rtt_client"] = t["rtt_client"] if t["client_valid"] else None
+
+
 def merge(table: dict, flows: np.ndarray, lo: int):
     """Add one chunk's records (packet numbers relative to `lo`) to the file's table."""
     for f in flows:
@@ -132,7 +164,7 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
     starts = np.array([lo for lo, _ in parts] + [0], np.int64)
     timed = a.idle is not None
     on_device = 0 < a.top <= abi.FLOW_TOP_MAX_K and not a.hosts   # the top comes from the device (--idle with --top is refused)
-    stamped = timed or (on_device and a.by == "duration") or a.hosts
+    stamped = timed or (on_device and a.by == "duration") or a.hosts or a.stats
     if stamped:   # a record's header is the 16 bytes before its data: ts_sec, ts_frac in the file's byte order
         head = np.stack([data[off - 16 + k] for k in range(8)], axis=1).astype(np.uint64) if len(off) else np.zeros((0, 8), np.uint64)
         order = (3, 2, 1, 0) if info["swapped"] else (0, 1, 2, 3)
@@ -140,7 +172,7 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         ts = word(0) * np.uint64(unit) + word(4)
     rows = []
 
-    def lines(recs, side=None):
+    def lines(recs, side=None, stat=None):
         for k, f in enumerate(recs):
             v = [int(f["packets"][0]), int(f["packets"][1]), int(f["bytes"][0]), int(f["bytes"][1]),
                  int(starts[f["first_batch"]]) + int(f["first"]), int(starts[f["last_batch"]]) + int(f["last"])]
@@ -154,6 +186,8 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
                 r["tcp_flags_fwd"], r["tcp_flags_rev"] = f"0x{fwd:02x}", f"0x{rev:02x}"
                 r["tcp_state"] = abi.TCP_STATE_NAMES[abi.flow_tcp_state(fwd, rev, flags)]
                 r["syn"], r["fin"], r["rst"] = int(t["syn_packets"]), int(t["fin_packets"]), int(t["rst_packets"])
+            if stat is not None:
+                describe_stats(r, stat[k], v[0:2], v[2:4], bool(flags & abi.FLOWTAB_BIDIRECTIONAL))
             rows.append(r)
 
     if a.tcp and timed:
@@ -165,10 +199,21 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
     if timed:
         d_ts, d_xscratch, d_xres, d_exp = ctx.alloc(max(16, max_n * 8)), ctx.alloc(xneed), ctx.alloc(32), ctx.alloc(104 * cap)
         bufs += [d_ts, d_xscratch, d_xres, d_exp]
-    if a.tcp:   # the side table, zeroed once; the update's flow ids feed it
-        d_ids, d_tcp, d_tres = ctx.alloc(max(16, max_n * 4)), ctx.alloc(16 * cap), ctx.alloc(32)
+    if a.tcp or a.stats:   # the update's flow ids feed the side tables
+        d_ids = ctx.alloc(max(16, max_n * 4))
+        bufs.append(d_ids)
+    if a.stats:   # the statistics, zeroed once; with --idle they follow the expire's remap
+        d_stat, d_sres = ctx.alloc(128 * cap), ctx.alloc(32)
+        d_stat.zero()
+        bufs += [d_stat, d_sres]
+        if timed:
+            mneed = abi.flow_track_side_move_scratch_bytes(cap, 128)
+            d_remap, d_mscratch, d_exp_stat = ctx.alloc(4 * cap), ctx.alloc(mneed), ctx.alloc(128 * cap)
+            bufs += [d_remap, d_mscratch, d_exp_stat]
+    if a.tcp:   # the side table, zeroed once
+        d_tcp, d_tres = ctx.alloc(16 * cap), ctx.alloc(32)
         d_tcp.zero()
-        bufs += [d_ids, d_tcp, d_tres]
+        bufs += [d_tcp, d_tres]
         if timed:
             d_exp_tcp = ctx.alloc(16 * cap)
             bufs.append(d_exp_tcp)
@@ -197,20 +242,26 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         if filters:
             ctx.run_device(batch, abi.Outputs(None, 0, d_ver.ptr, None, None, None))
         ctx.flow_track_update(d_state, batch, d_scratch, need, d_res, select=d_ver if filters else None,
-                              ts=d_ts if stamped else None, flow_id=d_ids if a.tcp else None)
+                              ts=d_ts if stamped else None, flow_id=d_ids if a.tcp or a.stats else None)
         if a.tcp:
             ctx.flow_tcp_update(batch, d_ids, flags, d_tcp, cap, d_tres)
+        if a.stats:
+            ctx.flow_stat_update(batch, d_ids, flags, d_stat, cap, d_sres, ts=d_ts)
         if timed:   # what aged out is printed now: its count and records come back, nothing else
             if a.tcp:
                 ctx.flow_track_expire_tcp(d_state, int(ts[hi - 1]), int(a.idle * unit), closed, d_tcp, d_xscratch, xneed, d_xres,
-                                          expired=d_exp, expired_cap=cap, expired_tcp=d_exp_tcp)
+                                          expired=d_exp, expired_cap=cap, expired_tcp=d_exp_tcp, remap=d_remap if a.stats else None)
             else:
-                ctx.flow_track_expire(d_state, int(ts[hi - 1]), int(a.idle * unit), d_xscratch, xneed, d_xres, expired=d_exp, expired_cap=cap)
+                ctx.flow_track_expire(d_state, int(ts[hi - 1]), int(a.idle * unit), d_xscratch, xneed, d_xres, expired=d_exp, expired_cap=cap,
+                                      remap=d_remap if a.stats else None)
+            if a.stats:   # the statistics of the flows that stay move up, those of the flows that leave come out
+                ctx.flow_track_side_move(d_stat, 128, cap, d_remap, d_xres, d_mscratch, mneed, expired_side=d_exp_stat, expired_cap=cap)
             ctx.synchronize()
             x = abi.FlowTrackExpireResult.from_bytes(d_xres.download(np.zeros(32, np.uint8))).as_dict()
             if x["n_expired"]:
                 lines(d_exp.download(np.zeros(104 * x["n_expired"], np.uint8)).view(abi.FlowTrackRec),
-                      d_exp_tcp.download(np.zeros(16 * x["n_expired"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None)
+                      d_exp_tcp.download(np.zeros(16 * x["n_expired"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None,
+                      d_exp_stat.download(np.zeros(128 * x["n_expired"], np.uint8)).view(abi.FlowStatRec) if a.stats else None)
     if on_device:   # behind the last update and side table update, on their stream
         ctx.flow_track_top(d_state, TOP_BY[a.by], a.top, d_tscratch, tneed, d_top_res, top=d_top, tcp=d_tcp if a.tcp else None,
                            top_tcp=d_top_tcp if a.tcp else None)
@@ -241,7 +292,8 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
     elif hdr["n_flows"]:
         both = d_state.download(np.zeros(lay["records"] + 104 * hdr["n_flows"], np.uint8))
         lines(both[lay["records"]:].view(abi.FlowTrackRec),
-              d_tcp.download(np.zeros(16 * hdr["n_flows"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None)
+              d_tcp.download(np.zeros(16 * hdr["n_flows"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None,
+              d_stat.download(np.zeros(128 * hdr["n_flows"], np.uint8)).view(abi.FlowStatRec) if a.stats else None)
     totals["selected"], totals["no_key"] = hdr["selected_packets"], hdr["none_packets"]
     abi.Context.flow_track_forget(d_state)   # before its memory goes back
     for b in bufs:
@@ -295,6 +347,7 @@ def main():
     ap.add_argument("--closed-idle", type=float, default=None, metavar="SECONDS")
     ap.add_argument("--by", choices=tuple(TOP_BY) + ("flows",), default=None)
     ap.add_argument("--hosts", action="store_true")
+    ap.add_argument("--stats", action="store_true")
     a = ap.parse_args()
     if a.chunk_packets < 0 or a.top < 0:
         raise SystemExit("--chunk-packets / --top: want a positive count")
@@ -308,6 +361,8 @@ def main():
         raise SystemExit("--closed-idle: want a time in seconds >= 0, with --tcp and --idle")
     if a.flow_cap < 0:
         raise SystemExit("--flow-cap: want a positive count")
+    if a.stats and (not a.track or a.top or a.hosts):
+        raise SystemExit("--stats: only with --track, and without --top and --hosts")
     if a.hosts and (not a.track or a.idle is not None):
         raise SystemExit("--hosts: only with --track, and without --idle")
     if a.hosts and a.by is not None and (a.by not in HOSTS_BY or not a.top):
@@ -348,6 +403,8 @@ def main():
         ctx.close()
     rows = [describe(k[0], k[1], v) for k, v in table.items()] if tracked is None else tracked   # insertion order: by first packet
     columns = COLUMNS + (("first_ts", "last_ts") if a.idle is not None else ()) + (TCP_COLUMNS if a.tcp else ())
+    if a.stats:
+        columns += STAT_COLUMNS + (RTT_COLUMNS if a.bidirectional else ())
     if a.hosts:   # host records in order of first appearance; a top is sorted here (stable: ties stay in that order)
         columns = HOST_COLUMNS + (HOST_TCP_COLUMNS if a.tcp else ())
         if a.top:
