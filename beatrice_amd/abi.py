@@ -629,6 +629,94 @@ def flow_track_side_move_host(side: np.ndarray, remap, result: dict, expired_cap
     return None if gone is None else gone[:min(result["n_expired"], expired_cap)]
 
 
+# bt_flow_mark_select_*: the flag and the ops that combine the marked packets with a base selection
+FLOW_MARK_ALL_BITS = 0x1
+FLOW_MARK_SET, FLOW_MARK_AND, FLOW_MARK_OR, FLOW_MARK_ANDNOT = range(4)
+
+# numpy view of bt_flow_mark_rec (32 B): record f of a mark table belongs to flow number f
+FlowMarkRec = np.dtype({
+    "names": ["marks", "hit_packets", "hit_bytes", "first_hit_ts_c", "last_hit_ts"],
+    "formats": ["<u4", "<u4", "<u8", "<u8", "<u8"],
+    "offsets": [0, 4, 8, 16, 24],
+    "itemsize": 32,
+})
+
+
+class FlowMarkUpdate(ctypes.Structure):
+    """bt_flow_mark_update (24 B): the mark bits, per-packet timestamps or one for the batch."""
+    _fields_ = [("mark", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("ts", ctypes.c_void_p), ("batch_ts", ctypes.c_uint64)]
+
+
+class FlowMarkResult(_Counts):
+    """bt_flow_mark_result (32 B): the counts of a mark table update."""
+    _fields_ = [("n", ctypes.c_uint32), ("hit_packets", ctypes.c_uint32), ("marked_packets", ctypes.c_uint32),
+                ("unkeyed_hits", ctypes.c_uint32), ("bad_ids", ctypes.c_uint32), ("new_marked_flows", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+class FlowMarkSelectOpts(ctypes.Structure):
+    """bt_flow_mark_select_opts (16 B)."""
+    _fields_ = [("mask", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("op", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class FlowMarkSelectResult(_Counts):
+    """bt_flow_mark_select_result (32 B): the counts of a selection by marks."""
+    _fields_ = [("n", ctypes.c_uint32), ("n_marked", ctypes.c_uint32), ("n_out", ctypes.c_uint32), ("bad_ids", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 4)]
+
+
+def flow_mark_update_host(desc, flow_id, hit, mark: int, table: np.ndarray, ts=None, batch_ts: int = 0) -> dict:
+    """bt_flow_mark_update_host (host only): the packets desc (packed descriptors) lists whose bit is
+    set in `hit` (verdict-layout u64 words, None = all) raise `mark` on the record of their flow
+    number flow_id[i] in `table` (FlowMarkRec, in place), stamped ts[i] (or batch_ts). Returns the
+    result dict."""
+    d = np.ascontiguousarray(desc, np.uint64)
+    n = len(d)
+    ids = np.ascontiguousarray(flow_id, np.uint32)
+    h = None if hit is None else np.ascontiguousarray(hit, np.uint64)
+    t = None if ts is None else np.ascontiguousarray(ts, np.uint64)
+    if (len(ids) != n or table.dtype != FlowMarkRec or not table.flags["C_CONTIGUOUS"] or (t is not None and len(t) != n)
+            or (h is not None and len(h) < (n + 63) // 64)):
+        raise ValueError("flow_mark_update_host: one flow_id (and ts) per descriptor, ceil(n/64) hit words and a contiguous "
+                         "FlowMarkRec table")
+    res = FlowMarkResult()
+    upd = FlowMarkUpdate(mark, 0, t.ctypes.data if t is not None and n else None, batch_ts)
+    _check(lib().bt_flow_mark_update_host(d.ctypes.data if n else None, n, ids.ctypes.data if n else None,
+                                          h.ctypes.data if h is not None and len(h) else None, ctypes.byref(upd),
+                                          table.ctypes.data if len(table) else None, len(table), ctypes.addressof(res)))
+    return res.as_dict()
+
+
+def flow_mark_select_host(flow_id, table: np.ndarray, mask: int, op: int = FLOW_MARK_SET, flags: int = 0, base=None, out=None) -> tuple:
+    """bt_flow_mark_select_host (host only): the verdict-layout selection of the packets whose flow
+    number flow_id[i] carries a bit of `mask` (with FLOW_MARK_ALL_BITS: every bit) in `table`
+    (FlowMarkRec), combined with `base` by a FLOW_MARK_* op. out: ceil(n/64) u64 words to write (may
+    be base itself), made when None. Returns (out, result dict)."""
+    ids = np.ascontiguousarray(flow_id, np.uint32)
+    n = len(ids)
+    nw = (n + 63) // 64
+    if out is None:
+        out = np.zeros(nw, np.uint64)
+    if (table.dtype != FlowMarkRec or not table.flags["C_CONTIGUOUS"] or out.dtype != np.uint64 or len(out) < nw
+            or not out.flags["C_CONTIGUOUS"] or (base is not None and (base.dtype != np.uint64 or len(base) < nw
+                                                                         or not base.flags["C_CONTIGUOUS"]))):
+        raise ValueError("flow_mark_select_host: a contiguous FlowMarkRec table and ceil(n/64) contiguous u64 words for base and out")
+    res = FlowMarkSelectResult()
+    opts = FlowMarkSelectOpts(mask, flags, op, 0)
+    _check(lib().bt_flow_mark_select_host(ids.ctypes.data if n else None, n, table.ctypes.data if len(table) else None, len(table),
+                                          ctypes.byref(opts), base.ctypes.data if base is not None and len(base) else None,
+                                          out.ctypes.data if len(out) else None, ctypes.addressof(res)))
+    return out, res.as_dict()
+
+
+def decode_flow_mark(rec) -> dict:
+    """One FlowMarkRec in plain values: the complemented first stamp undone, None where the flow was never hit."""
+    r = np.ascontiguousarray(rec, FlowMarkRec).reshape(1)[0]
+    return {"marks": int(r["marks"]), "hit_packets": int(r["hit_packets"]), "hit_bytes": int(r["hit_bytes"]),
+            "first_hit_ts": None if int(r["first_hit_ts_c"]) == 0 else 0xFFFFFFFFFFFFFFFF - int(r["first_hit_ts_c"]),
+            "last_hit_ts": int(r["last_hit_ts"]) if int(r["hit_packets"]) else None}
+
+
 # bt_flow_track_top_*: the metric a top-K query orders by, and its limit on k
 FLOW_TOP_BYTES, FLOW_TOP_PACKETS, FLOW_TOP_DURATION, FLOW_TOP_TCP_SYN, FLOW_TOP_TCP_RST = range(5)
 FLOW_TOP_MAX_K = 4096
@@ -854,6 +942,8 @@ EXPORTS = [
     "bt_time_flow_hosts_host",
     "bt_flow_stat_update_device", "bt_flow_stat_update_host", "bt_flow_stat_rtt", "bt_time_flow_stat",
     "bt_flow_track_side_move_scratch_bytes", "bt_flow_track_side_move_device", "bt_flow_track_side_move_host",
+    "bt_flow_mark_update_device", "bt_flow_mark_update_host", "bt_flow_mark_select_device", "bt_flow_mark_select_host",
+    "bt_time_flow_mark",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -949,6 +1039,12 @@ def lib() -> ctypes.CDLL:
         "bt_flow_track_side_move_scratch_bytes": (ctypes.c_int, [u32, u32, ctypes.POINTER(u64)]),
         "bt_flow_track_side_move_device": (ctypes.c_int, [vp, ctypes.POINTER(FlowSideMove), vp, u64, vp]),
         "bt_flow_track_side_move_host": (ctypes.c_int, [ctypes.POINTER(FlowSideMove)]),
+        "bt_flow_mark_update_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, ctypes.POINTER(FlowMarkUpdate), vp, u32, vp, vp]),
+        "bt_flow_mark_update_host": (ctypes.c_int, [vp, u32, vp, vp, ctypes.POINTER(FlowMarkUpdate), vp, u32, vp]),
+        "bt_flow_mark_select_device": (ctypes.c_int, [vp, vp, u32, vp, u32, ctypes.POINTER(FlowMarkSelectOpts), vp, vp, vp, vp]),
+        "bt_flow_mark_select_host": (ctypes.c_int, [vp, u32, vp, u32, ctypes.POINTER(FlowMarkSelectOpts), vp, vp, vp]),
+        "bt_time_flow_mark": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, ctypes.POINTER(FlowMarkUpdate), vp, u32, vp,
+                                             ctypes.POINTER(FlowMarkSelectOpts), vp, vp, vp, u32, vp, vp]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -1391,7 +1487,34 @@ class Context:
         m = FlowSideMove(ptr(side), ptr(expired_side), ptr(remap), ptr(result), rec_bytes, flow_cap, expired_cap, 0)
         _check(lib().bt_flow_track_side_move_device(self.h, ctypes.byref(m), ptr(scratch), scratch_bytes, stream))
 
+    def flow_mark_update(self, batch: Batch, flow_id, hit, mark: int, table, flow_cap: int, result, ts=None, batch_ts: int = 0,
+                         stream=None):
+        """bt_flow_mark_update_device: the packets of `batch` whose bit is set in `hit` (verdict-layout
+        words on the device, out.verdict of a filter call; None = all) raise `mark` on the record of
+        their flow number flow_id[i] in `table` (flow_cap FlowMarkRec on the device, zeroed once by
+        the caller), with their count, frame lengths and first / last timestamp (ts[i], device, n
+        u64, or batch_ts). result: 32 B (FlowMarkResult), 8-byte aligned. Pointers are addresses or
+        DeviceBuffers. Asynchronous on `stream`: enqueue it behind the calls that wrote flow_id and hit."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        upd = FlowMarkUpdate(mark, 0, ptr(ts), batch_ts)
+        _check(lib().bt_flow_mark_update_device(self.h, ctypes.byref(batch), ptr(flow_id), ptr(hit), ctypes.byref(upd), ptr(table),
+                                                flow_cap, ptr(result), stream))
+
+    def flow_mark_select(self, flow_id, n: int, table, flow_cap: int, mask: int, out_select, result, op: int = FLOW_MARK_SET,
+                         flags: int = 0, base=None, stream=None):
+        """bt_flow_mark_select_device: out_select (ceil(n/64) u64 words on the device, verdict layout)
+        = the packets whose flow number flow_id[i] carries a bit of `mask` (with FLOW_MARK_ALL_BITS:
+        every bit) in `table`, combined with `base` by a FLOW_MARK_* op (base may be out_select).
+        result: 32 B (FlowMarkSelectResult), 8-byte aligned. Asynchronous on `stream`: enqueue it
+        behind the call that wrote flow_id and the updates of the table it should see."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        opts = FlowMarkSelectOpts(mask, flags, op, 0)
+        _check(lib().bt_flow_mark_select_device(self.h, ptr(flow_id), n, ptr(table), flow_cap, ctypes.byref(opts), ptr(base),
+                                                ptr(out_select), ptr(result), stream))
+
     # the host-only forms beside their device forms
+    flow_mark_update_host = staticmethod(flow_mark_update_host)
+    flow_mark_select_host = staticmethod(flow_mark_select_host)
     flow_stat_update_host = staticmethod(flow_stat_update_host)
     flow_stat_rtt = staticmethod(flow_stat_rtt)
     flow_track_side_move_scratch_bytes = staticmethod(flow_track_side_move_scratch_bytes)

@@ -271,6 +271,13 @@ int run_flow_tcp(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, uin
 int run_flow_stat(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, uint32_t table_flags, const bt_flow_track_update* upd,
                   bt_flow_stat_rec* stat, uint32_t flow_cap, bt_flow_stat_result* result, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 
+// bt_flowmark_host.cpp (bt_timing.cpp's bt_time_flow_mark times the same launches)
+int run_flow_mark(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* hit, const bt_flow_mark_update* upd,
+                  bt_flow_mark_rec* table, uint32_t flow_cap, bt_flow_mark_result* result, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+int run_flow_mark_select(bt_ctx* c, const uint32_t* flow_id, uint32_t n, const bt_flow_mark_rec* table, uint32_t flow_cap,
+                         const bt_flow_mark_select_opts* opts, const uint64_t* base, uint64_t* out, bt_flow_mark_select_result* result,
+                         hipStream_t st, hipEvent_t e0, hipEvent_t e1);
+
 // bt_flowtop_host.cpp (bt_timing.cpp's bt_time_flow_top times the same launches)
 int run_flow_track_top(bt_ctx* c, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
                        uint64_t scratch_bytes, const bt_flow_top_out* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1);

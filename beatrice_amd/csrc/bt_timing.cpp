@@ -254,6 +254,34 @@ int bt_time_flow_stat(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id
     return BT_OK;
 }
 
+int bt_time_flow_mark(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* hit, const bt_flow_mark_update* upd,
+                      bt_flow_mark_rec* table, uint32_t flow_cap, bt_flow_mark_result* result, const bt_flow_mark_select_opts* opts,
+                      const uint64_t* base, uint64_t* out_select, bt_flow_mark_select_result* sel_result, uint32_t iters, float* update_ms,
+                      float* select_ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !frames || !frames->n || !iters || (!update_ms && !select_ms))
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, iters)) return rc;
+    for (uint32_t pass = 0; pass < 2u; ++pass) {
+        float* const ms = pass ? select_ms : update_ms;
+        if (!ms) continue;
+        for (uint32_t i = 0; i < iters; ++i) {
+            hipEvent_t e0 = c->timing.tev[2 * i], e1 = c->timing.tev[2 * i + 1];
+            const int rc = pass ? run_flow_mark_select(c, flow_id, frames->n, table, flow_cap, opts, base, out_select, sel_result, c->stream, e0, e1)
+                                : run_flow_mark(c, frames, flow_id, hit, upd, table, flow_cap, result, c->stream, e0, e1);
+            if (rc) {
+                (void)hipStreamSynchronize(c->stream);
+                return rc;
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    }
+    return BT_OK;
+}
+
 int bt_time_flow_top(bt_ctx* c, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
                      uint64_t scratch_bytes, const bt_flow_top_out* out, uint32_t iters, float* ms) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return

@@ -56,6 +56,25 @@ __device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
     return v;
 }
 
+// Is this lane the only lane of the wave that is `in` with its key? slots: 256 bytes of LDS of the
+// wave's own. Every lane that is `in` writes its number into the byte its key picks; the lane whose
+// number stays is the slot's winner, a lane that finds another lane of its own key there marks the
+// slot, and a winner whose slot is unmarked has no second lane of its key, since one key is one
+// slot. A lane that merely shares a slot with another key is not alone. Call it wave-uniformly.
+// (bt_flowstat_update holds the same statements inline: through this helper its code differs by an
+// instruction.)
+__device__ __forceinline__ bool wave_alone(uint8_t* slots, bool in, uint32_t key, uint32_t lane) {
+    uint8_t* const my_slot = &slots[key & 255u];
+    if (in) *my_slot = (uint8_t)lane;
+    wave_lds_sync();
+    const uint32_t won = in ? *my_slot : lane;                         // the lane whose number stayed in the slot
+    const uint32_t won_key = (uint32_t)__shfl((int)key, (int)won);     // ... and its key
+    wave_lds_sync();
+    if (in && won != lane && won_key == key) *my_slot = 0xFFu;         // the winner's key has a second lane
+    wave_lds_sync();
+    return in && won == lane && *my_slot == (uint8_t)lane;
+}
+
 // The exclusive scan of v over a block of Threads threads, and the sum in *total; sh: Threads / 64 words.
 template <uint32_t Threads>
 __device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* sh, uint32_t* total) {

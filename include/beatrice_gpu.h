@@ -92,7 +92,8 @@ extern "C" {
  * bt_flow_track_top_host, bt_flow_track_hosts_scratch_bytes, bt_flow_track_hosts_device,
  * bt_flow_track_hosts_host, bt_flow_stat_update_device, bt_flow_stat_update_host,
  * bt_flow_stat_rtt, bt_flow_track_side_move_scratch_bytes, bt_flow_track_side_move_device,
- * bt_flow_track_side_move_host. */
+ * bt_flow_track_side_move_host, bt_flow_mark_update_device, bt_flow_mark_update_host,
+ * bt_flow_mark_select_device, bt_flow_mark_select_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -961,6 +962,92 @@ int  bt_flow_stat_rtt(const bt_flow_stat_rec* rec, bt_flow_stat_rtt_out* out);  
 int  bt_flow_track_side_move_scratch_bytes(uint32_t flow_cap, uint32_t rec_bytes, uint64_t* bytes);
 int  bt_flow_track_side_move_device(bt_ctx* ctx, const bt_flow_side_move* m, void* scratch, uint64_t scratch_bytes, void* stream);
 int  bt_flow_track_side_move_host(const bt_flow_side_move* m);
+
+/* ---- per-flow mark side table: flows marked by a verdict, whole sessions selected -----------
+ * The way back from a verdict to the packets of its connection: a filter call's verdict raises a
+ * mark on the flows of its passing packets (bt_flow_mark_update_device), and a selection is built
+ * from the marks of every packet's flow (bt_flow_mark_select_device), for the pack, the fan-out,
+ * the flow table or the tracker. The table is flow_cap records bt_flow_mark_rec of the caller's
+ * memory, 8-byte aligned; record f belongs to flow number f of a per-batch table or of a tracker.
+ * The caller zeroes it once (all-zero = never hit); there is no init call. Every field is an OR,
+ * an integer sum or a maximum (the earliest stamp is stored complemented, as the statistics'
+ * stamps: zero reads as none, so a hit at 2^64 - 1 reads as no first hit), so an update is exact
+ * and bit-identical from run to run however many packets are taken in parallel.
+ * bt_flow_mark_update_device: `hit` has the verdict-word layout (bit i % 64 of word i / 64;
+ * out->verdict of a filter call is one; NULL = every packet in [0, n) is a hit; bits at or above
+ * n are ignored). flow_id is read for hit packets only. A hit packet i with flow_id[i] < flow_cap
+ * adds to record flow_id[i], with t = upd->ts[i] (device, n entries; only hit packets' are read)
+ * or upd->batch_ts when ts is NULL:
+ *   marks |= upd->mark; hit_packets += 1; hit_bytes += min(len, 65535), the frame length as
+ *   bytes[] of the flow record; first_hit_ts_c = max(.., ~t); last_hit_ts = max(.., t).
+ * Only lengths are read from `frames` (both descriptor formats and fixed stride, as the pack and
+ * the tally take them), never frame bytes, and only those of hit packets with an id below
+ * flow_cap. *result: hit_packets = the hit bits in [0, n); marked_packets = the hits that reached
+ * a record; unkeyed_hits = the hits whose id is a BT_FLOW_ID_* sentinel; bad_ids = the hits whose
+ * id is neither a sentinel nor below flow_cap (ids of packets that are no hit are not looked at);
+ * new_marked_flows = the flows whose marks lacked a bit of upd->mark before the call and took a
+ * hit in it, exactly. Ordering, stream, n == 0 and the refusals are bt_flow_tcp_update_device's
+ * (there is no table_flags), with these refused too: a null upd, upd->mark == 0, a non-zero
+ * upd->reserved, a misaligned ts or table (8 bytes). Nothing is written outside
+ * mark_table[0 .. flow_cap) and *result.
+ * bt_flow_mark_select_device: m(i) is true when flow_id[i] < flow_cap and mark_table[flow_id[i]]
+ * .marks & opts->mask is non-zero, or with BT_FLOW_MARK_ALL_BITS equals opts->mask. opts->op
+ * combines it with `base` (verdict layout, ceil(n/64) words; optional with BT_FLOW_MARK_SET,
+ * where it is not read, required otherwise): SET out = m; AND out = base & m; OR out = base | m;
+ * ANDNOT out = base & ~m. out_select is ceil(n/64) words whose bits at or above n are written as
+ * 0 whatever base holds there; base == out_select is allowed, in place (any other overlap is
+ * not). *result: n_marked = the packets with m true, n_out = the bits set in out_select, bad_ids
+ * = the packets in [0, n) whose id is neither a sentinel nor below flow_cap. The marks are read,
+ * never written. Asynchronous on `stream` (NULL = the context's), behind the call that wrote
+ * flow_id and every update of the table it should see; no allocation, no host synchronisation;
+ * n == 0 writes *result in stream order and no word. BT_E_INVALID_ARGUMENT before the context or
+ * any HIP call: a null opts, mask == 0, unknown flags, an unknown op, a non-zero reserved; a null
+ * flow_id or out_select (with n > 0), mark_table (with flow_cap > 0) or result; misalignment
+ * (flow_id 4 bytes; mark_table, base, out_select and result 8); a missing base where the op needs
+ * one; then a null context.
+ * bt_flow_mark_update_host / bt_flow_mark_select_host: the same on the calling thread, no context
+ * and no device, bit-identical; packed descriptors, upd->ts in host memory.
+ * Expiring: there is no call of its own. The table goes through bt_flow_track_side_move_device
+ * with rec_bytes = 32 behind the expire, as any side table does. */
+#define BT_FLOW_MARK_ALL_BITS 0x1u   /* bt_flow_mark_select_opts.flags: every bit of mask, not any */
+enum { BT_FLOW_MARK_SET = 0, BT_FLOW_MARK_AND = 1, BT_FLOW_MARK_OR = 2, BT_FLOW_MARK_ANDNOT = 3 };
+
+typedef struct bt_flow_mark_rec {     /* 32 B, 8-byte aligned; all-zero = never hit */
+    uint32_t marks;            /* OR of upd->mark over the updates in which a hit packet of the flow took part */
+    uint32_t hit_packets;      /* hit packets of the flow; mod 2^32 */
+    uint64_t hit_bytes;        /* their frame lengths, min(len, 65535) as bytes[] of the flow record; mod 2^64 */
+    uint64_t first_hit_ts_c;   /* ~(earliest hit timestamp): zero reads as none, as the statistics' stamps */
+    uint64_t last_hit_ts;      /* latest hit timestamp */
+} bt_flow_mark_rec;
+
+typedef struct bt_flow_mark_update {  /* 24 B */
+    uint32_t mark, reserved;   /* mark != 0; reserved 0 */
+    const uint64_t* ts;        /* optional, n entries (device form: device memory) */
+    uint64_t batch_ts;         /* every hit's timestamp when ts is NULL */
+} bt_flow_mark_update;
+
+typedef struct bt_flow_mark_result {  /* 32 B, device-visible, 8-byte aligned */
+    uint32_t n, hit_packets, marked_packets, unkeyed_hits, bad_ids, new_marked_flows, reserved[2];
+} bt_flow_mark_result;
+
+typedef struct bt_flow_mark_select_opts { uint32_t mask, flags, op, reserved; } bt_flow_mark_select_opts;
+
+typedef struct bt_flow_mark_select_result {   /* 32 B, device-visible, 8-byte aligned */
+    uint32_t n, n_marked, n_out, bad_ids, reserved[4];
+} bt_flow_mark_select_result;
+
+int  bt_flow_mark_update_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id /* device, n */,
+                                const uint64_t* hit /* NULL = all n */, const bt_flow_mark_update* upd,
+                                bt_flow_mark_rec* mark_table, uint32_t flow_cap, bt_flow_mark_result* result, void* stream);
+int  bt_flow_mark_update_host(const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_id, const uint64_t* hit,
+                              const bt_flow_mark_update* upd /* ts: host */, bt_flow_mark_rec* mark_table, uint32_t flow_cap,
+                              bt_flow_mark_result* result);
+int  bt_flow_mark_select_device(bt_ctx* ctx, const uint32_t* flow_id /* device, n */, uint32_t n,
+                                const bt_flow_mark_rec* mark_table, uint32_t flow_cap, const bt_flow_mark_select_opts* opts,
+                                const uint64_t* base, uint64_t* out_select, bt_flow_mark_select_result* result, void* stream);
+int  bt_flow_mark_select_host(const uint32_t* flow_id, uint32_t n, const bt_flow_mark_rec* mark_table, uint32_t flow_cap,
+                              const bt_flow_mark_select_opts* opts, const uint64_t* base, uint64_t* out_select,
+                              bt_flow_mark_select_result* result);
 
 /* ---- top-K flows of a tracker: the largest flows by a measure, selected on the device ------
  * bt_flow_track_top_device: the k largest flows of the tracker at `state` by opts->metric,

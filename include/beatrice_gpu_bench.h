@@ -130,6 +130,16 @@ int  bt_time_flow_tcp(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_
 int  bt_time_flow_stat(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id, uint32_t table_flags,
                        const bt_flow_track_update* upd, bt_flow_stat_rec* stat, uint32_t flow_cap,
                        bt_flow_stat_result* result, uint32_t iters, float* ms);
+/* With update_ms: bt_flow_mark_update_device `iters` times on the context's stream into the same
+ * mark table; with select_ms, after those: bt_flow_mark_select_device `iters` times over that table.
+ * ms[i] = call i's kernel, from an event pair recorded by its own dispatch (the 32-byte memset of
+ * the result in front of it is outside the pair). From the second update on every mark bit and
+ * stamp is already there. Either of update_ms / select_ms may be NULL; its arguments are then unused. */
+int  bt_time_flow_mark(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* hit,
+                       const bt_flow_mark_update* upd, bt_flow_mark_rec* mark_table, uint32_t flow_cap,
+                       bt_flow_mark_result* result, const bt_flow_mark_select_opts* opts, const uint64_t* base,
+                       uint64_t* out_select, bt_flow_mark_select_result* sel_result, uint32_t iters,
+                       float* update_ms, float* select_ms);
 /* What the tracker replaces, `iters` times: copy_ms[i] = the n_flows records of a per-batch table
  * (flows, on the device) copied to pinned host memory (wall clock, the wait included), merge_ms[i]
  * = those records merged into the host tracker state at host_state (bt_flow_track_init_host's) on
