@@ -717,6 +717,77 @@ def decode_flow_mark(rec) -> dict:
             "last_hit_ts": int(r["last_hit_ts"]) if int(r["hit_packets"]) else None}
 
 
+# bt_flow_seq_*: the flag, and what seq / byte_off hold for a packet that was not numbered
+FLOW_SEQ_KEEP_UNKEYED = 0x1
+FLOW_SEQ_NONE = 0xFFFFFFFF
+FLOW_SEQ_MAX = 0xFFFFFFFE
+FLOW_SEQ_OFF_NONE = 0xFFFFFFFFFFFFFFFF
+
+# numpy view of bt_flow_seq_rec (16 B): record f of a sequence table belongs to flow number f
+FlowSeqRec = np.dtype({"names": ["packets", "bytes"], "formats": ["<u8", "<u8"], "offsets": [0, 8], "itemsize": 16})
+
+
+class FlowSeqOpts(ctypes.Structure):
+    """bt_flow_seq_opts (32 B): the per-flow limits (0 = none) and FLOW_SEQ_* flags."""
+    _fields_ = [("max_packets", ctypes.c_uint64), ("max_bytes", ctypes.c_uint64), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 3)]
+
+
+class FlowSeqOut(ctypes.Structure):
+    """bt_flow_seq_out (24 B): the three optional outputs."""
+    _fields_ = [("seq", ctypes.c_void_p), ("byte_off", ctypes.c_void_p), ("out_select", ctypes.c_void_p)]
+
+
+class FlowSeqResult(_Counts):
+    """bt_flow_seq_result (64 B): the counts of a numbering call."""
+    _fields_ = [("n", ctypes.c_uint32), ("selected", ctypes.c_uint32), ("numbered", ctypes.c_uint32), ("unkeyed", ctypes.c_uint32),
+                ("bad_ids", ctypes.c_uint32), ("kept", ctypes.c_uint32), ("flows", ctypes.c_uint32), ("new_flows", ctypes.c_uint32),
+                ("numbered_bytes", ctypes.c_uint64), ("kept_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 2)]
+
+
+def flow_seq_scratch_bytes(n: int, flow_cap: int) -> int:
+    """bt_flow_seq_scratch_bytes (host only)."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_seq_scratch_bytes(n, flow_cap, ctypes.byref(b)))
+    return b.value
+
+
+def flow_seq_host(desc, flow_id, select, table: np.ndarray, max_packets: int = 0, max_bytes: int = 0, flags: int = 0,
+                  seq=None, byte_off=None, out_select=None) -> dict:
+    """bt_flow_seq_host (host only): the packets desc (packed descriptors) lists whose bit is set in
+    `select` (verdict-layout u64 words, None = all) and whose flow number flow_id[i] is below
+    len(table) are numbered inside their flow against `table` (FlowSeqRec, in place). seq (n u32),
+    byte_off (n u64) and out_select (ceil(n/64) u64 words, may be `select`) are written where given.
+    Returns the result dict."""
+    d = np.ascontiguousarray(desc, np.uint64)
+    n = len(d)
+    nw = (n + 63) // 64
+    ids = np.ascontiguousarray(flow_id, np.uint32)
+    sel = select
+    if sel is not None and (sel.dtype != np.uint64 or not sel.flags["C_CONTIGUOUS"] or len(sel) < nw):
+        raise ValueError("flow_seq_host: ceil(n/64) contiguous u64 select words")
+    for arr, dt, need in ((seq, np.uint32, n), (byte_off, np.uint64, n), (out_select, np.uint64, nw)):
+        if arr is not None and (arr.dtype != dt or not arr.flags["C_CONTIGUOUS"] or len(arr) < need):
+            raise ValueError("flow_seq_host: contiguous outputs of n u32, n u64 and ceil(n/64) u64")
+    if len(ids) != n or table.dtype != FlowSeqRec or not table.flags["C_CONTIGUOUS"]:
+        raise ValueError("flow_seq_host: one flow_id per descriptor and a contiguous FlowSeqRec table")
+    at = lambda x: x.ctypes.data if x is not None and len(x) else None  # noqa: E731
+    res = FlowSeqResult()
+    opts = FlowSeqOpts(max_packets, max_bytes, flags, (ctypes.c_uint32 * 3)(0, 0, 0))
+    out = FlowSeqOut(at(seq), at(byte_off), at(out_select))
+    _check(lib().bt_flow_seq_host(at(d), n, at(ids), at(sel), ctypes.byref(opts), at(table), len(table), ctypes.byref(out),
+                                  ctypes.addressof(res)))
+    return res.as_dict()
+
+
+def decode_flow_seq(seq, byte_off) -> list:
+    """seq and byte_off of a numbering call in plain values: (packets before, bytes before) per
+    packet, None for a packet that was not numbered; a seq of FLOW_SEQ_MAX means "at least"."""
+    s = np.asarray(seq, np.uint32)
+    b = np.asarray(byte_off, np.uint64)
+    return [None if int(x) == FLOW_SEQ_NONE else (int(x), int(y)) for x, y in zip(s, b)]
+
+
 # bt_flow_track_top_*: the metric a top-K query orders by, and its limit on k
 FLOW_TOP_BYTES, FLOW_TOP_PACKETS, FLOW_TOP_DURATION, FLOW_TOP_TCP_SYN, FLOW_TOP_TCP_RST = range(5)
 FLOW_TOP_MAX_K = 4096
@@ -944,6 +1015,7 @@ EXPORTS = [
     "bt_flow_track_side_move_scratch_bytes", "bt_flow_track_side_move_device", "bt_flow_track_side_move_host",
     "bt_flow_mark_update_device", "bt_flow_mark_update_host", "bt_flow_mark_select_device", "bt_flow_mark_select_host",
     "bt_time_flow_mark",
+    "bt_flow_seq_scratch_bytes", "bt_flow_seq_device", "bt_flow_seq_host", "bt_time_flow_seq",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -1045,6 +1117,12 @@ def lib() -> ctypes.CDLL:
         "bt_flow_mark_select_host": (ctypes.c_int, [vp, u32, vp, u32, ctypes.POINTER(FlowMarkSelectOpts), vp, vp, vp]),
         "bt_time_flow_mark": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, ctypes.POINTER(FlowMarkUpdate), vp, u32, vp,
                                              ctypes.POINTER(FlowMarkSelectOpts), vp, vp, vp, u32, vp, vp]),
+        "bt_flow_seq_scratch_bytes": (ctypes.c_int, [u32, u32, ctypes.POINTER(ctypes.c_uint64)]),
+        "bt_flow_seq_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, ctypes.POINTER(FlowSeqOpts), vp, u32,
+                                              ctypes.POINTER(FlowSeqOut), vp, ctypes.c_uint64, vp, vp]),
+        "bt_flow_seq_host": (ctypes.c_int, [vp, u32, vp, vp, ctypes.POINTER(FlowSeqOpts), vp, u32, ctypes.POINTER(FlowSeqOut), vp]),
+        "bt_time_flow_seq": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, ctypes.POINTER(FlowSeqOpts), vp, u32,
+                                            ctypes.POINTER(FlowSeqOut), vp, ctypes.c_uint64, vp, u32, vp, vp]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -1512,8 +1590,27 @@ class Context:
         _check(lib().bt_flow_mark_select_device(self.h, ptr(flow_id), n, ptr(table), flow_cap, ctypes.byref(opts), ptr(base),
                                                 ptr(out_select), ptr(result), stream))
 
+    def flow_seq(self, batch: Batch, flow_id, select, table, flow_cap: int, scratch, scratch_bytes: int, result,
+                 max_packets: int = 0, max_bytes: int = 0, flags: int = 0, seq=None, byte_off=None, out_select=None, stream=None):
+        """bt_flow_seq_device: the packets of `batch` whose bit is set in `select` (verdict-layout words
+        on the device; None = all) and whose flow number flow_id[i] is below flow_cap are numbered
+        inside their flow against `table` (flow_cap FlowSeqRec on the device, zeroed once by the
+        caller): seq (n u32) and byte_off (n u64) get the flow's packets and bytes before each, and
+        out_select (ceil(n/64) u64 words, may be `select`) the packets within max_packets / max_bytes
+        per flow (0 = no limit), with FLOW_SEQ_KEEP_UNKEYED also the selected packets without a flow.
+        scratch: flow_seq_scratch_bytes(n, flow_cap) bytes, 256-byte aligned. result: 64 B
+        (FlowSeqResult), 8-byte aligned. Pointers are addresses or DeviceBuffers. Asynchronous on
+        `stream`: enqueue it behind the calls that wrote flow_id and select."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        opts = FlowSeqOpts(max_packets, max_bytes, flags, (ctypes.c_uint32 * 3)(0, 0, 0))
+        out = FlowSeqOut(ptr(seq), ptr(byte_off), ptr(out_select))
+        _check(lib().bt_flow_seq_device(self.h, ctypes.byref(batch), ptr(flow_id), ptr(select), ctypes.byref(opts), ptr(table),
+                                        flow_cap, ctypes.byref(out), ptr(scratch), scratch_bytes, ptr(result), stream))
+
     # the host-only forms beside their device forms
     flow_mark_update_host = staticmethod(flow_mark_update_host)
+    flow_seq_host = staticmethod(flow_seq_host)
+    flow_seq_scratch_bytes = staticmethod(flow_seq_scratch_bytes)
     flow_mark_select_host = staticmethod(flow_mark_select_host)
     flow_stat_update_host = staticmethod(flow_stat_update_host)
     flow_stat_rtt = staticmethod(flow_stat_rtt)

@@ -278,6 +278,11 @@ int run_flow_mark_select(bt_ctx* c, const uint32_t* flow_id, uint32_t n, const b
                          const bt_flow_mark_select_opts* opts, const uint64_t* base, uint64_t* out, bt_flow_mark_select_result* result,
                          hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 
+// bt_flowseq_host.cpp (bt_timing.cpp's bt_time_flow_seq times the same launches; ev: nullptr or five events)
+int run_flow_seq(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select, const bt_flow_seq_opts* opts,
+                 bt_flow_seq_rec* table, uint32_t flow_cap, const bt_flow_seq_out* out, void* scratch, uint64_t scratch_bytes,
+                 bt_flow_seq_result* result, hipStream_t st, void* const* ev);
+
 // bt_flowtop_host.cpp (bt_timing.cpp's bt_time_flow_top times the same launches)
 int run_flow_track_top(bt_ctx* c, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
                        uint64_t scratch_bytes, const bt_flow_top_out* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1);

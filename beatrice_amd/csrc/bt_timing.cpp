@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "bt_ctx.h"
+#include "bt_flowseq.h"
 #include "bt_flowtrack.h"
 #include "bt_hip_util.h"
 
@@ -278,6 +279,39 @@ int bt_time_flow_mark(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
         for (uint32_t i = 0; i < iters; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->timing.tev[2 * i], c->timing.tev[2 * i + 1]));
+    }
+    return BT_OK;
+}
+
+int bt_time_flow_seq(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select, const bt_flow_seq_opts* opts,
+                     bt_flow_seq_rec* table, uint32_t flow_cap, const bt_flow_seq_out* out, void* scratch, uint64_t scratch_bytes,
+                     bt_flow_seq_result* result, uint32_t iters, float* ms, float* phase_ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !frames || !frames->n || !iters || !ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, (5u * iters + 1u) / 2u)) return rc;
+    for (uint32_t i = 0; i < iters; ++i) {
+        void* ev[5];
+        for (uint32_t k = 0; k < 5u; ++k) ev[k] = c->timing.tev[5 * i + k];
+        if (int rc = run_flow_seq(c, frames, flow_id, select, opts, table, flow_cap, out, scratch, scratch_bytes, result, c->stream, ev)) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const bool sorted = bt::fs_passes(flow_cap) != 0u;   // without a pass the sort's event is not recorded
+    for (uint32_t i = 0; i < iters; ++i) {
+        hipEvent_t* const e = &c->timing.tev[5 * i];
+        HIP_TRY(hipEventElapsedTime(&ms[i], e[0], e[4]));
+        if (!phase_ms) continue;
+        float* const ph = phase_ms + 4 * i;
+        ph[1] = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ph[0], e[0], sorted ? e[1] : e[2]));
+        if (sorted) HIP_TRY(hipEventElapsedTime(&ph[1], e[1], e[2]));
+        HIP_TRY(hipEventElapsedTime(&ph[2], e[2], e[3]));
+        HIP_TRY(hipEventElapsedTime(&ph[3], e[3], e[4]));
     }
     return BT_OK;
 }

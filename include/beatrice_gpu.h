@@ -93,7 +93,8 @@ extern "C" {
  * bt_flow_track_hosts_host, bt_flow_stat_update_device, bt_flow_stat_update_host,
  * bt_flow_stat_rtt, bt_flow_track_side_move_scratch_bytes, bt_flow_track_side_move_device,
  * bt_flow_track_side_move_host, bt_flow_mark_update_device, bt_flow_mark_update_host,
- * bt_flow_mark_select_device, bt_flow_mark_select_host. */
+ * bt_flow_mark_select_device, bt_flow_mark_select_host, bt_flow_seq_scratch_bytes,
+ * bt_flow_seq_device, bt_flow_seq_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -1048,6 +1049,71 @@ int  bt_flow_mark_select_device(bt_ctx* ctx, const uint32_t* flow_id /* device, 
 int  bt_flow_mark_select_host(const uint32_t* flow_id, uint32_t n, const bt_flow_mark_rec* mark_table, uint32_t flow_cap,
                               const bt_flow_mark_select_opts* opts, const uint64_t* base, uint64_t* out_select,
                               bt_flow_mark_select_result* result);
+
+/* ---- per-flow sequence side table: a packet's position inside its flow, a per-flow cut-off ---
+ * The one flow primitive that depends on order: every selected packet with a flow number learns
+ * how many packets and bytes of its flow came before it, and "the first K packets / the first B
+ * bytes of every connection" becomes a selection for the pack, the fan-out or the tracker. The
+ * table is flow_cap records bt_flow_seq_rec of the caller's memory, 8-byte aligned; record f
+ * belongs to flow number f of a per-batch table or of a tracker. The caller zeroes it once
+ * (all-zero = nothing numbered yet); there is no init call.
+ * Numbering: packet i is numbered when its bit is set in `select` (verdict-word layout, NULL =
+ * every packet in [0, n); bits at or above n are ignored) and flow_id[i] < flow_cap. With f its
+ * flow, P and B table[f].packets and .bytes before the call, p(i) the numbered packets j < i of
+ * flow f in this batch and b(i) the sum of their min(len, 65535) (the flow records' length rule):
+ * before_pk(i) = P + p(i), before_by(i) = B + b(i), mod 2^64. Order within a batch is the packet
+ * index; order across batches is the order of the calls on the stream.
+ * out->seq[i] = min(before_pk(i), BT_FLOW_SEQ_MAX), out->byte_off[i] = before_by(i); every packet
+ * in [0, n) that is not numbered (not selected, a sentinel id, a bad id) gets BT_FLOW_SEQ_NONE /
+ * BT_FLOW_SEQ_OFF_NONE. keep(i): i is numbered, and max_packets == 0 or before_pk(i) <
+ * max_packets, and max_bytes == 0 or before_by(i) < max_bytes: the packet that crosses the byte
+ * limit is still kept, the next one is not; the decision is on the 64-bit values, not on the
+ * saturated seq. out->out_select (verdict layout, ceil(n/64) words): bit i = keep(i), or with
+ * BT_FLOW_SEQ_KEEP_UNKEYED also "selected and flow_id[i] is a BT_FLOW_ID_* sentinel"; bits at or
+ * above n are written as 0; out_select == select is allowed, in place (any other overlap is not).
+ * Each of the three outputs is optional. After the call table[f].packets and .bytes have grown by
+ * the flow's numbered packets and bytes of this batch, kept or not. Nothing is written outside
+ * table[0 .. flow_cap), the requested outputs, the scratch and *result.
+ * *result: selected = the select bits in [0, n); numbered, numbered_bytes = the numbered packets
+ * and their bytes; unkeyed = the selected packets with a sentinel id; bad_ids = the selected
+ * packets whose id is neither a sentinel nor below flow_cap; kept = the bits out_select holds or
+ * would hold; kept_bytes = the min(len, 65535) of kept numbered packets; flows = the distinct
+ * flows numbered in this call, exactly; new_flows = those whose record had packets == 0 before.
+ * Only lengths are read from `frames` (both descriptor formats and fixed stride), never frame
+ * bytes, and only those of numbered packets; flow_id is read for selected packets only.
+ * Asynchronous on `stream` (NULL = the context's), behind the call that wrote flow_id; no
+ * allocation, no host synchronisation; n == 0 writes *result in stream order and nothing else.
+ * scratch: bt_flow_seq_scratch_bytes(n, flow_cap) bytes of device memory, 256-byte aligned; the
+ * call initialises what it reads. Every output is exact and bit-identical from run to run.
+ * BT_E_INVALID_ARGUMENT before the context or any HIP call: a null opts, out or result; unknown
+ * flags; a non-zero reserved; a null flow_id or frames (with n > 0) or table (with flow_cap > 0);
+ * misalignment (flow_id, seq 4 bytes; table, select, byte_off, out_select, result 8; scratch 256);
+ * a scratch that is too small; then a null context.
+ * bt_flow_seq_host: the same on the calling thread, no context, no device and no scratch,
+ * bit-identical; packed descriptors.
+ * Expiring: there is no call of its own. The table goes through bt_flow_track_side_move_device
+ * with rec_bytes = 16 behind the expire, as any side table does. */
+#define BT_FLOW_SEQ_KEEP_UNKEYED 0x1u          /* opts.flags: a selected packet whose id is a BT_FLOW_ID_* sentinel is kept */
+#define BT_FLOW_SEQ_NONE      0xFFFFFFFFu      /* seq[i] of a packet that was not numbered */
+#define BT_FLOW_SEQ_MAX       0xFFFFFFFEu      /* seq[i] saturates here */
+#define BT_FLOW_SEQ_OFF_NONE  0xFFFFFFFFFFFFFFFFull
+
+typedef struct bt_flow_seq_rec   { uint64_t packets, bytes; } bt_flow_seq_rec;          /* 16 B; all-zero = nothing numbered yet */
+typedef struct bt_flow_seq_opts  { uint64_t max_packets, max_bytes; uint32_t flags, reserved[3]; } bt_flow_seq_opts;   /* 32 B; 0 = no limit */
+typedef struct bt_flow_seq_out   { uint32_t* seq; uint64_t* byte_off; uint64_t* out_select; } bt_flow_seq_out;         /* each optional */
+typedef struct bt_flow_seq_result {            /* 64 B, device-visible, 8-byte aligned */
+    uint32_t n, selected, numbered, unkeyed, bad_ids, kept, flows, new_flows;
+    uint64_t numbered_bytes, kept_bytes, reserved[2];
+} bt_flow_seq_result;
+
+int  bt_flow_seq_scratch_bytes(uint32_t n, uint32_t flow_cap, uint64_t* bytes);       /* host only */
+int  bt_flow_seq_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id /* device, n */,
+                        const uint64_t* select /* NULL = all n */, const bt_flow_seq_opts* opts, bt_flow_seq_rec* table,
+                        uint32_t flow_cap, const bt_flow_seq_out* out, void* scratch, uint64_t scratch_bytes,
+                        bt_flow_seq_result* result, void* stream);
+int  bt_flow_seq_host(const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_id, const uint64_t* select,
+                      const bt_flow_seq_opts* opts, bt_flow_seq_rec* table, uint32_t flow_cap, const bt_flow_seq_out* out,
+                      bt_flow_seq_result* result);
 
 /* ---- top-K flows of a tracker: the largest flows by a measure, selected on the device ------
  * bt_flow_track_top_device: the k largest flows of the tracker at `state` by opts->metric,

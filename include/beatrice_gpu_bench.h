@@ -140,6 +140,15 @@ int  bt_time_flow_mark(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow
                        bt_flow_mark_result* result, const bt_flow_mark_select_opts* opts, const uint64_t* base,
                        uint64_t* out_select, bt_flow_mark_select_result* sel_result, uint32_t iters,
                        float* update_ms, float* select_ms);
+/* bt_flow_seq_device `iters` times on the context's stream into the same table (which keeps growing)
+ * and the same scratch; ms[i] = call i's kernels, from the first one's start to the last one's end,
+ * events recorded by the kernels' own dispatches (the 64-byte memset of *result in front is outside).
+ * phase_ms (optional, 4 * iters): call i's compaction, sort (every pass; 0 without one), segmented
+ * scan and emit + table update, in that order, between the starts of their first kernels. */
+int  bt_time_flow_seq(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select,
+                      const bt_flow_seq_opts* opts, bt_flow_seq_rec* table, uint32_t flow_cap, const bt_flow_seq_out* out,
+                      void* scratch, uint64_t scratch_bytes, bt_flow_seq_result* result, uint32_t iters, float* ms,
+                      float* phase_ms);
 /* What the tracker replaces, `iters` times: copy_ms[i] = the n_flows records of a per-batch table
  * (flows, on the device) copied to pinned host memory (wall clock, the wait included), merge_ms[i]
  * = those records merged into the host tracker state at host_state (bt_flow_track_init_host's) on
