@@ -16,8 +16,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import flow_ref as fr  # noqa: E402
 import flowseq_ref as qr  # noqa: E402
+import flowtrack_ref as fkr  # noqa: E402
 from beatrice_amd import abi  # noqa: E402
-from test_gpu_flowtab import FORMATS, Guarded, Source, select_words  # noqa: E402
+from conftest import load_golden  # noqa: E402
+from test_gpu_flowtab import FORMATS, POISON, Guarded, Source, golden_keys, select_words  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -328,3 +330,80 @@ def test_continuity_across_calls(gpu_ctx):
     finally:
         src.free()
         d_ids.free()
+
+
+@pytest.mark.parametrize("name", ["http", "edge"])
+def test_the_table_goes_through_a_device_expire_by_the_side_move(gpu_ctx, name):
+    """The GPU twin of test_flowseq.py's host case: a device tracker numbers two batches; the sequence table
+    follows a device expire by bt_flow_track_side_move_device with rec_bytes = 16, and a third batch goes on
+    where its flows were. Flow numbers and the remap come from flowtrack_ref, positions from flowseq_ref;
+    every call is enqueued on one stream and waited for once."""
+    ctx = gpu_ctx
+    g, _ = load_golden(name)
+    n0 = len(g["desc"])
+    half = n0 // 2
+    desc = g["desc"].astype(np.uint64)
+    lens = (desc >> np.uint64(48)).astype(np.int64)
+    keys = golden_keys(name)
+    parts = [(slice(0, half), 100), (slice(half, n0), 5000), (slice(half, n0), 5001)]
+    ref, want = fkr.Tracker(n0, 0), np.zeros(n0, qr.SEQ_REC)
+    lay = abi.flow_track_layout(n0, 0)
+    need = max([abi.flow_track_scratch_bytes(n0), abi.flow_seq_scratch_bytes(n0, n0), abi.flow_track_expire_scratch_bytes(n0),
+                abi.flow_track_side_move_scratch_bytes(n0, 16)])
+    state, table, scratch = Guarded(ctx, lay["total"]), Guarded(ctx, 16 * n0), Guarded(ctx, need)
+    exp = {"expired": Guarded(ctx, 104 * n0), "side": Guarded(ctx, 16 * n0), "remap": Guarded(ctx, 4 * n0), "res": Guarded(ctx, 32)}
+    srcs, outs, wants = [], [], []
+    st = ctx.stream_create()
+    started = False
+    try:
+        abi._check(abi.lib().bt_memset_d(ctx.h, table.ptr, 0, 16 * n0))
+        for k, (sl, ts) in enumerate(parts):
+            if k == 2:   # the restatement's expire between the second and the third batch
+                before = want.copy()
+                e = ref.expire(5000, 1000, n0)
+                r = e["result"]
+                assert r["n_expired"] > 0 and r["n_flows"] > 0
+                gone = before[:r["n_flows_before"]][e["remap"] == fkr.EXPIRED]
+                want[:] = 0
+                stay = e["remap"] != fkr.EXPIRED
+                want[e["remap"][stay]] = before[:r["n_flows_before"]][stay]
+            n = sl.stop - sl.start
+            ids = ref.update(keys[0][sl], keys[1][sl], keys[2][sl], lens[sl], None, None, ts)["flow_id"]
+            wants.append(qr.number(want, ids, lens[sl], None, 3) + (ids,))
+            srcs.append(Source(ctx, name, n, "packed", desc=desc[sl]))
+            outs.append({"ids": Guarded(ctx, 4 * n), "seq": Guarded(ctx, 4 * n), "off": Guarded(ctx, 8 * n), "words": Guarded(ctx, 8 * ((n + 63) // 64)),
+                         "track": Guarded(ctx, 64), "res": Guarded(ctx, 64)})
+        ctx.synchronize()
+        ctx.flow_track_init(state.ptr, lay["total"], n0, 0, 0, stream=st)
+        started = True
+        for k, (src, o, (sl, ts)) in enumerate(zip(srcs, outs, parts)):
+            if k == 2:
+                ctx.flow_track_expire(state.ptr, 5000, 1000, scratch.ptr, need, exp["res"].ptr, expired=exp["expired"].ptr, expired_cap=n0,
+                                      remap=exp["remap"].ptr, stream=st)
+                ctx.flow_track_side_move(table.ptr, 16, n0, exp["remap"].ptr, exp["res"].ptr, scratch.ptr, need, expired_side=exp["side"].ptr,
+                                         expired_cap=n0, stream=st)
+            ctx.flow_track_update(state.ptr, src.batch, scratch.ptr, need, o["track"].ptr, batch_ts=ts, flow_id=o["ids"].ptr, stream=st)
+            ctx.flow_seq(src.batch, o["ids"].ptr, None, table.ptr, n0, scratch.ptr, need, o["res"].ptr, max_packets=3, seq=o["seq"].ptr,
+                         byte_off=o["off"].ptr, out_select=o["words"].ptr, stream=st)
+        ctx.stream_synchronize(st)
+        ctx.synchronize()
+        scratch.read()   # its guards
+        for k, (o, (wseq, woff, wout, wres, ids)) in enumerate(zip(outs, wants)):
+            assert (o["ids"].read(np.uint32) == ids).all(), f"batch {k}: flow_id"
+            assert abi.FlowSeqResult.from_bytes(o["res"].read()).as_dict() == wres, f"batch {k}: result"
+            assert (o["seq"].read(np.uint32) == wseq).all() and (o["off"].read(np.uint64) == woff).all(), f"batch {k}: seq / byte_off"
+            assert (o["words"].read(np.uint64) == wout).all(), f"batch {k}: out_select"
+        res = abi.FlowTrackExpireResult.from_bytes(exp["res"].read()).as_dict()
+        assert res == r and (exp["remap"].read(np.uint32)[:r["n_flows_before"]] == e["remap"]).all()
+        side = exp["side"].read()
+        assert side[:16 * r["n_expired"]].tobytes() == gone.tobytes() and (side[16 * r["n_expired"]:] == POISON).all(), "the expired flows' records"
+        assert exp["expired"].read()[:104 * r["n_expired"]].tobytes() == e["expired"].tobytes()
+        assert table.read().tobytes() == want.tobytes(), "the table after the third batch"
+        keyed = wants[2][4] < n0
+        assert wants[2][3]["new_flows"] == 0 and (wants[2][0][keyed] >= 1).all()   # every flow of the second half survived with its count
+    finally:
+        if started:
+            abi.Context.flow_track_forget(state.ptr)
+        ctx.stream_destroy(st)
+        for b in [state, table, scratch, *exp.values(), *srcs] + [x for o in outs for x in o.values()]:
+            b.free()
