@@ -788,6 +788,84 @@ def decode_flow_seq(seq, byte_off) -> list:
     return [None if int(x) == FLOW_SEQ_NONE else (int(x), int(y)) for x, y in zip(s, b)]
 
 
+# numpy view of bt_flow_stream_rec (32 B): record f of a stream table belongs to flow number f
+FlowStreamRec = np.dtype({"names": ["d", "hit_packets", "stream_packets"], "formats": [("<u8", 2), ("<u4", 2), ("<u4", 2)],
+                          "offsets": [0, 16, 24], "itemsize": 32})
+
+
+class FlowStreamInfo(_Counts):
+    """bt_flow_stream_info (16 B): the blob's entry width W, the pattern's positions P, the tail T = P - 1 and the closure steps R."""
+    _fields_ = [("width", ctypes.c_uint32), ("positions", ctypes.c_uint32), ("tail", ctypes.c_uint32), ("closure", ctypes.c_uint32)]
+
+
+class FlowStreamOut(ctypes.Structure):
+    """bt_flow_stream_out (32 B): the optional hit words and the result."""
+    _fields_ = [("hit", ctypes.c_void_p), ("result", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2)]
+
+
+class FlowStreamResult(_Counts):
+    """bt_flow_stream_result (64 B): the counts of a stream matching call."""
+    _fields_ = [("n", ctypes.c_uint32), ("selected", ctypes.c_uint32), ("stream_packets", ctypes.c_uint32),
+                ("hit_packets", ctypes.c_uint32), ("unkeyed", ctypes.c_uint32), ("bad_ids", ctypes.c_uint32),
+                ("stream_bytes", ctypes.c_uint64), ("new_hit_flows", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+
+
+def flow_stream_compile(expression: str):
+    """bt_flow_stream_compile (host only): (blob as a u8 array, info dict) of a pattern the stream
+    matcher takes. BtError BT_E_NOT_IMPLEMENTED names the construct it refuses (+, *, {n,}, ^, $, \\b,
+    a pattern only the DFA takes, the always / never forms); BT_E_INVALID_ARGUMENT: not a regex."""
+    e = expression.encode()
+    size = ctypes.c_uint32(0)
+    info = FlowStreamInfo()
+    _check(lib().bt_flow_stream_compile(e, None, 0, ctypes.byref(size), ctypes.addressof(info)))
+    blob = np.zeros(size.value, np.uint8)
+    _check(lib().bt_flow_stream_compile(e, blob.ctypes.data, size.value, ctypes.byref(size), ctypes.addressof(info)))
+    return blob, info.as_dict()
+
+
+def flow_stream_scratch_bytes(n: int, flow_cap: int) -> int:
+    """bt_flow_stream_scratch_bytes (host only)."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_stream_scratch_bytes(n, flow_cap, ctypes.byref(b)))
+    return b.value
+
+
+def flow_stream_host(data, desc, flow_id, select, table_flags: int, pattern, table: np.ndarray, hit=None, nbytes=None) -> dict:
+    """bt_flow_stream_host (host only): the L4 payloads of the frames desc (packed descriptors) lists
+    in `data` whose bit is set in `select` (verdict-layout u64 words, None = all) and whose flow
+    number flow_id[i] is below len(table) are appended to their (flow, direction) streams, and
+    `pattern` (flow_stream_compile's blob) is matched across them against `table` (FlowStreamRec, in
+    place). hit (ceil(n/64) u64 words, may be `select`) gets the packets in which a match ends.
+    Returns the result dict."""
+    a = _byte_view(data)
+    keep = a if len(a) else np.zeros(1, np.uint8)
+    d = np.ascontiguousarray(desc, np.uint64)
+    n = len(d)
+    nw = (n + 63) // 64
+    ids = np.ascontiguousarray(flow_id, np.uint32)
+    pat = np.ascontiguousarray(pattern, np.uint8)
+    for arr in (select, hit):
+        if arr is not None and (arr.dtype != np.uint64 or not arr.flags["C_CONTIGUOUS"] or len(arr) < nw):
+            raise ValueError("flow_stream_host: ceil(n/64) contiguous u64 words for select and hit")
+    if len(ids) != n or table.dtype != FlowStreamRec or not table.flags["C_CONTIGUOUS"]:
+        raise ValueError("flow_stream_host: one flow_id per descriptor and a contiguous FlowStreamRec table")
+    at = lambda x: x.ctypes.data if x is not None and len(x) else None  # noqa: E731
+    res = FlowStreamResult()
+    out = FlowStreamOut(at(hit), ctypes.addressof(res), (ctypes.c_uint64 * 2)(0, 0))
+    _check(lib().bt_flow_stream_host(keep.ctypes.data, len(a) if nbytes is None else nbytes, at(d), n, at(ids), at(select),
+                                     table_flags, at(pat), len(pat), at(table), len(table), ctypes.byref(out)))
+    return res.as_dict()
+
+
+def decode_flow_stream(rec) -> dict:
+    """One FlowStreamRec in plain values, per direction: the matcher's state, the packets of the
+    stream and those in which a match ended."""
+    r = np.ascontiguousarray(rec, FlowStreamRec).reshape(1)[0]
+    return {"state": [int(r["d"][0]), int(r["d"][1])], "stream_packets": [int(r["stream_packets"][0]), int(r["stream_packets"][1])],
+            "hit_packets": [int(r["hit_packets"][0]), int(r["hit_packets"][1])],
+            "hit": bool(int(r["hit_packets"][0]) or int(r["hit_packets"][1]))}
+
+
 # bt_flow_track_top_*: the metric a top-K query orders by, and its limit on k
 FLOW_TOP_BYTES, FLOW_TOP_PACKETS, FLOW_TOP_DURATION, FLOW_TOP_TCP_SYN, FLOW_TOP_TCP_RST = range(5)
 FLOW_TOP_MAX_K = 4096
@@ -1016,6 +1094,8 @@ EXPORTS = [
     "bt_flow_mark_update_device", "bt_flow_mark_update_host", "bt_flow_mark_select_device", "bt_flow_mark_select_host",
     "bt_time_flow_mark",
     "bt_flow_seq_scratch_bytes", "bt_flow_seq_device", "bt_flow_seq_host", "bt_time_flow_seq",
+    "bt_flow_stream_compile", "bt_flow_stream_scratch_bytes", "bt_flow_stream_device", "bt_flow_stream_host",
+    "bt_time_flow_stream",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -1123,6 +1203,14 @@ def lib() -> ctypes.CDLL:
         "bt_flow_seq_host": (ctypes.c_int, [vp, u32, vp, vp, ctypes.POINTER(FlowSeqOpts), vp, u32, ctypes.POINTER(FlowSeqOut), vp]),
         "bt_time_flow_seq": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, ctypes.POINTER(FlowSeqOpts), vp, u32,
                                             ctypes.POINTER(FlowSeqOut), vp, ctypes.c_uint64, vp, u32, vp, vp]),
+        "bt_flow_stream_compile": (ctypes.c_int, [ctypes.c_char_p, vp, u32, ctypes.POINTER(u32), vp]),
+        "bt_flow_stream_scratch_bytes": (ctypes.c_int, [u32, u32, ctypes.POINTER(ctypes.c_uint64)]),
+        "bt_flow_stream_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, u32, vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
+                                                 ctypes.POINTER(FlowStreamOut), vp]),
+        "bt_flow_stream_host": (ctypes.c_int, [vp, ctypes.c_uint64, vp, u32, vp, vp, u32, vp, u32, vp, u32,
+                                               ctypes.POINTER(FlowStreamOut)]),
+        "bt_time_flow_stream": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, u32, vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
+                                               ctypes.POINTER(FlowStreamOut), u32, vp, vp]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -1607,7 +1695,28 @@ class Context:
         _check(lib().bt_flow_seq_device(self.h, ctypes.byref(batch), ptr(flow_id), ptr(select), ctypes.byref(opts), ptr(table),
                                         flow_cap, ctypes.byref(out), ptr(scratch), scratch_bytes, ptr(result), stream))
 
+    def flow_stream(self, batch: Batch, flow_id, select, table_flags: int, pattern, pattern_device, table, flow_cap: int,
+                    scratch, scratch_bytes: int, result, hit=None, stream=None):
+        """bt_flow_stream_device: the L4 payloads of the packets of `batch` whose bit is set in `select`
+        (verdict-layout words on the device; None = all) and whose flow number flow_id[i] is below
+        flow_cap are appended to their (flow, direction) streams, and `pattern` (flow_stream_compile's
+        blob on the host; pattern_device: a device copy of it, 8-byte aligned) is matched across
+        packet and batch boundaries against `table` (flow_cap FlowStreamRec on the device, zeroed
+        once by the caller). hit (ceil(n/64) u64 words, may be `select`) gets the packets in which a
+        match ends. scratch: flow_stream_scratch_bytes(n, flow_cap) bytes, 256-byte aligned. result:
+        64 B (FlowStreamResult), 8-byte aligned. Pointers are addresses or DeviceBuffers.
+        Asynchronous on `stream`: enqueue it behind the calls that wrote flow_id and select."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        pat = np.ascontiguousarray(pattern, np.uint8)
+        out = FlowStreamOut(ptr(hit), ptr(result), (ctypes.c_uint64 * 2)(0, 0))
+        _check(lib().bt_flow_stream_device(self.h, ctypes.byref(batch), ptr(flow_id), ptr(select), table_flags,
+                                           pat.ctypes.data if len(pat) else None, ptr(pattern_device), len(pat), ptr(table), flow_cap,
+                                           ptr(scratch), scratch_bytes, ctypes.byref(out), stream))
+
     # the host-only forms beside their device forms
+    flow_stream_host = staticmethod(flow_stream_host)
+    flow_stream_compile = staticmethod(flow_stream_compile)
+    flow_stream_scratch_bytes = staticmethod(flow_stream_scratch_bytes)
     flow_mark_update_host = staticmethod(flow_mark_update_host)
     flow_seq_host = staticmethod(flow_seq_host)
     flow_seq_scratch_bytes = staticmethod(flow_seq_scratch_bytes)

@@ -228,4 +228,14 @@ inline void flowseq_host(const bt_pkt_desc* desc, uint32_t n, const uint32_t* fl
 // start of the compaction, of the sort, of the scan and of the emit, and the end of the last kernel.
 int launch_flowseq(const FlowseqArgs& a, void* stream, void* const* ev = nullptr);
 
+// The sort alone, for another primitive that orders (key, index) pairs (bt_flowstream.hip): the
+// same kernels, launched from here so that there is one copy of them. Of `a` only nchunks, head,
+// parts, a, b, dcnt, drel, dwcnt and dstart are used.
+//   launch_flowseq_join  the exclusive scan of parts[c].count into parts[c].rel and head->m;
+//   launch_flowseq_sort  `passes` stable passes of 8 bits over the head->m pairs at a.a, low digit
+//                        first; *sorted = where they end up (a.a or a.b). e_start: nullptr, or a
+//                        timing event recorded at the start of the first pass's first kernel.
+void launch_flowseq_join(const FlowseqArgs& a, void* stream);
+void launch_flowseq_sort(const FlowseqArgs& a, uint32_t passes, void* stream, void* e_start, const FsPair** sorted);
+
 }  // namespace bt

@@ -404,6 +404,27 @@ __global__ __launch_bounds__(kFsJoinThreads) void bt_flowseq_sjoin(FlowseqArgs a
     }
 }
 
+void launch_flowseq_join(const FlowseqArgs& a, void* stream) {
+    launch(bt_flowseq_join, dim3(1), dim3(kFsJoinThreads), 0, reinterpret_cast<hipStream_t>(stream), nullptr, nullptr, a);
+}
+
+void launch_flowseq_sort(const FlowseqArgs& a, uint32_t passes, void* stream, void* e_start, const FsPair** sorted) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(a.nchunks), block(kFsThreads), one(1), join(kFsJoinThreads);
+    const FsPair* src = a.a;
+    FsPair* dst = a.b;
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        const uint32_t shift = pass * kFsDigitBits;
+        launch(bt_flowseq_digits, grid, block, 0, st, pass == 0 ? reinterpret_cast<hipEvent_t>(e_start) : nullptr, nullptr, a, src, shift);
+        launch(bt_flowseq_djoin, one, join, 0, st, nullptr, nullptr, a);
+        launch(bt_flowseq_scatter, grid, block, 0, st, nullptr, nullptr, a, src, dst, shift);
+        FsPair* const was = const_cast<FsPair*>(src);
+        src = dst;
+        dst = was;
+    }
+    *sorted = src;
+}
+
 int launch_flowseq(const FlowseqArgs& a, void* stream, void* const* ev) {
     if (a.n == 0 || a.nchunks == 0) return BT_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

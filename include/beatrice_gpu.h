@@ -94,7 +94,8 @@ extern "C" {
  * bt_flow_stat_rtt, bt_flow_track_side_move_scratch_bytes, bt_flow_track_side_move_device,
  * bt_flow_track_side_move_host, bt_flow_mark_update_device, bt_flow_mark_update_host,
  * bt_flow_mark_select_device, bt_flow_mark_select_host, bt_flow_seq_scratch_bytes,
- * bt_flow_seq_device, bt_flow_seq_host. */
+ * bt_flow_seq_device, bt_flow_seq_host, bt_flow_stream_compile, bt_flow_stream_scratch_bytes,
+ * bt_flow_stream_device, bt_flow_stream_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -1114,6 +1115,82 @@ int  bt_flow_seq_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flo
 int  bt_flow_seq_host(const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_id, const uint64_t* select,
                       const bt_flow_seq_opts* opts, bt_flow_seq_rec* table, uint32_t flow_cap, const bt_flow_seq_out* out,
                       bt_flow_seq_result* result);
+
+/* ---- per-flow stream matching: a payload pattern across packet boundaries ------------------
+ * The PAYLOAD filter decides a pattern per packet, over the reference's 100-byte window. This
+ * primitive decides it per stream: a match may begin in one packet of a flow and end in a later
+ * one, in this batch or in an earlier call.
+ * The stream of (flow f, direction d) is the concatenation, in packet order within a batch and in
+ * call order across batches, of the L4 payloads of its contributing packets. It is arrival order,
+ * not TCP sequence order: retransmissions and reordering are not undone.
+ * Packet i contributes when its bit is set in `select` (verdict-word layout, NULL = every packet in
+ * [0, n); bits at or above n are ignored), flow_id[i] < flow_cap, the walk of bt_flow_fanout_device
+ * finds a whole TCP or UDP header under the flow key's rule (the statistics table's BT_FSEEN_L4
+ * rule: protocol 6 or 17, the whole 20 / 8 header bytes in the frame, IPv4 neither MF nor a
+ * fragment offset) and its payload length is > 0. With l3 and l4 the offsets of the two headers:
+ * the payload starts at l4 + 4 * (tcp[12] >> 4) for TCP and at l4 + 8 for UDP, and ends at
+ * min(frame length, l3 + IPv4 total_length), for IPv6 at min(frame length, l3 + 40 +
+ * payload_length): Ethernet padding is not part of the stream, a snapped capture contributes what
+ * it holds, and an end at or before the start is no payload. The direction d is the TCP side
+ * table's under table_flags (0 without BT_FLOWTAB_BIDIRECTIONAL). Frame bytes are read under the
+ * fan-out's read rule: a byte at or past `bytes` reads as zero. A BT_FLOW_ID_* sentinel
+ * contributes nothing; any other selected id >= flow_cap counts in bad_ids.
+ * The pattern is a blob of bt_flow_stream_compile: bt_payload_dfa_compile_ex(expression, 0) where
+ * the result is the bit-parallel form with form == 1 (a search) and flags == 0 (no repeatable
+ * position, no anchor, no $). Such a pattern has bounded memory: with P positions its state after
+ * any byte is a function of the last P - 1 stream bytes, so every piece of every stream is
+ * matched on its own behind its T = P - 1 <= 63 preceding bytes. Everything else returns
+ * BT_E_NOT_IMPLEMENTED (+, *, {n,}, ^, $, \b, patterns only the DFA takes, the always / never
+ * forms); what std::regex rejects returns BT_E_INVALID_ARGUMENT. info: width = the blob's W,
+ * positions = P, tail = T, closure = R.
+ * out->hit (optional; verdict layout, ceil(n/64) words, bits at or above n zero): bit i is set iff
+ * some match of the pattern ends at a stream byte that belongs to packet i's payload, wherever it
+ * began in the same flow and direction. hit == select is allowed, in place.
+ * table: flow_cap records bt_flow_stream_rec of the caller's memory, 8-byte aligned, zeroed once
+ * (all-zero = nothing seen); d[dir] = the matcher's state after the stream's last contributing
+ * byte; hit_packets / stream_packets per direction, mod 2^32. It goes through an expire by
+ * bt_flow_track_side_move_device with rec_bytes = 32; there is no expire call of its own.
+ * *out->result: selected = the select bits in [0, n); stream_packets, stream_bytes = the
+ * contributing packets and their payload bytes; hit_packets = the hit bits; unkeyed = the selected
+ * packets with a sentinel id; bad_ids as above; new_hit_flows = the flows with a hit in this call
+ * whose record had hit_packets[0] == hit_packets[1] == 0 before it, exactly.
+ * Asynchronous on `stream` (NULL = the context's), behind the call that wrote flow_id; no
+ * allocation, no host synchronisation; n == 0 writes *result in stream order and nothing else.
+ * pattern is host memory (checked before any HIP call), pattern_device a device copy of the same
+ * pattern_bytes bytes, 8-byte aligned. scratch: bt_flow_stream_scratch_bytes(n, flow_cap) bytes of
+ * device memory, 256-byte aligned; the call initialises what it reads. flow_cap <= 2^31. Nothing
+ * is written outside table[0 .. flow_cap), out->hit, the scratch and *out->result; every output is
+ * exact and bit-identical from run to run.
+ * BT_E_INVALID_ARGUMENT before the context or any HIP call: a null frames, out, out->result,
+ * pattern or pattern_device; a null flow_id (with n > 0) or table (with flow_cap > 0);
+ * misalignment (flow_id 4 bytes; table, select, hit, result, pattern_device 8; scratch 256);
+ * unknown table_flags; a non-zero reserved; a BT_BATCH_PREFIXES / BT_BATCH_LEAN batch; flow_cap
+ * above 2^31; a blob the predicate refuses (BT_E_NOT_IMPLEMENTED); a scratch that is too small;
+ * then a null context.
+ * bt_flow_stream_host: the same on the calling thread, no context, no device and no scratch,
+ * bit-identical; packed descriptors. */
+typedef struct bt_flow_stream_rec {            /* 32 B; all-zero = nothing seen */
+    uint64_t d[2];                             /* the matcher's state after the last contributing byte, per direction */
+    uint32_t hit_packets[2], stream_packets[2];
+} bt_flow_stream_rec;
+typedef struct bt_flow_stream_info { uint32_t width, positions, tail, closure; } bt_flow_stream_info;   /* W, P, T = P - 1, R */
+typedef struct bt_flow_stream_out { uint64_t* hit; struct bt_flow_stream_result* result; uint64_t reserved[2]; } bt_flow_stream_out;
+typedef struct bt_flow_stream_result {         /* 64 B, device-visible, 8-byte aligned */
+    uint32_t n, selected, stream_packets, hit_packets, unkeyed, bad_ids;
+    uint64_t stream_bytes;
+    uint32_t new_hit_flows, reserved[7];
+} bt_flow_stream_result;
+
+int  bt_flow_stream_compile(const char* expression, void* blob, uint32_t cap, uint32_t* size,
+                            bt_flow_stream_info* info /* optional */);                 /* host only */
+int  bt_flow_stream_scratch_bytes(uint32_t n, uint32_t flow_cap, uint64_t* bytes);    /* host only */
+int  bt_flow_stream_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id /* device, n */,
+                           const uint64_t* select /* NULL = all n */, uint32_t table_flags, const void* pattern /* host */,
+                           const void* pattern_device, uint32_t pattern_bytes, bt_flow_stream_rec* table, uint32_t flow_cap,
+                           void* scratch, uint64_t scratch_bytes, const bt_flow_stream_out* out, void* stream);
+int  bt_flow_stream_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_id,
+                         const uint64_t* select, uint32_t table_flags, const void* pattern, uint32_t pattern_bytes,
+                         bt_flow_stream_rec* table, uint32_t flow_cap, const bt_flow_stream_out* out);
 
 /* ---- top-K flows of a tracker: the largest flows by a measure, selected on the device ------
  * bt_flow_track_top_device: the k largest flows of the tracker at `state` by opts->metric,

@@ -149,6 +149,15 @@ int  bt_time_flow_seq(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_
                       const bt_flow_seq_opts* opts, bt_flow_seq_rec* table, uint32_t flow_cap, const bt_flow_seq_out* out,
                       void* scratch, uint64_t scratch_bytes, bt_flow_seq_result* result, uint32_t iters, float* ms,
                       float* phase_ms);
+/* bt_flow_stream_device `iters` times on the context's stream into the same table (whose streams keep
+ * growing) and the same scratch; ms[i] = call i's kernels, from the first one's start to the last
+ * one's end, events recorded by the kernels' own dispatches (the two memsets in front are outside).
+ * phase_ms (optional, 4 * iters): call i's classification + compaction, sort (every pass), link +
+ * match, and commit, in that order. */
+int  bt_time_flow_stream(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select,
+                         uint32_t table_flags, const void* pattern, const void* pattern_device, uint32_t pattern_bytes,
+                         bt_flow_stream_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes,
+                         const bt_flow_stream_out* out, uint32_t iters, float* ms, float* phase_ms);
 /* What the tracker replaces, `iters` times: copy_ms[i] = the n_flows records of a per-batch table
  * (flows, on the device) copied to pinned host memory (wall clock, the wait included), merge_ms[i]
  * = those records merged into the host tracker state at host_state (bt_flow_track_init_host's) on

@@ -2,8 +2,12 @@
 --invert, drop those connections whole): the session view of tools/pcap_filter.py, decided on the GPU.
 
 Usage: python tools/pcap_sessions.py --in a.pcap --out b.pcap --filter TYPE:EXPR[:PRIO] ...
-                                     [--bidirectional] [--l3-only] [--invert] [--flow-cap N] [--chunk PACKETS]
+                                     [--stream EXPR] [--bidirectional] [--l3-only] [--invert] [--flow-cap N] [--chunk PACKETS]
   --filter         as tools/pcap_filter.py takes it
+  --stream EXPR    also (or, without --filter, only) select the connections in whose payload stream EXPR matches,
+                   wherever the match lies: across TCP segments and past a packet's first 100 bytes
+                   (bt_flow_stream_device, per direction, in arrival order). EXPR must have bounded memory: no +, *,
+                   {n,}, ^, $ or \\b; anything else ends the run with the construct's name, never a per-packet match
   --bidirectional  both directions of a conversation are one session (BT_FLOWTAB_BIDIRECTIONAL)
   --l3-only        never key on ports (BT_FLOWTAB_L3_ONLY): a session is a pair of addresses
   --invert         write the complement: every packet that is in no session with a passing packet
@@ -24,7 +28,11 @@ file, n / 8 bytes, are complemented here between the passes): a packet is writte
 pass and its flow carries no mark, exactly the packets the default run leaves out. Only the
 packed bytes come back. The output records are verbatim and in order behind the input's global
 header, as bt_pcap_filter writes them. A program with a slot the GPU cannot decide (BT_K_HOST) is refused.
-Prints one JSON line: packets, hit_packets, flows, marked_flows, unkeyed_hits, written_packets, written_bytes.
+With --stream, pass one per chunk is: the filter (if any), the tracker update, bt_flow_stream_device over all packets
+against one stream table for the whole file, bt_flow_mark_update_device with the stream's hits (and, with a filter, a
+second one with the verdict), then pass two as above; without a filter the stream's hit words stand where the verdict's do.
+Prints one JSON line: packets, hit_packets, flows, marked_flows, unkeyed_hits, written_packets, written_bytes, and with
+--stream also stream_packets, stream_bytes, stream_hit_packets.
 """
 from __future__ import annotations
 
@@ -52,6 +60,7 @@ def main():
     ap.add_argument("--in", dest="src", required=True)
     ap.add_argument("--out", dest="dst", required=True)
     ap.add_argument("--filter", action="append", default=[], metavar="TYPE:EXPR[:PRIO]")
+    ap.add_argument("--stream", default=None, metavar="EXPR")
     ap.add_argument("--bidirectional", action="store_true")
     ap.add_argument("--l3-only", action="store_true")
     ap.add_argument("--invert", action="store_true")
@@ -61,9 +70,15 @@ def main():
     a = ap.parse_args()
     if a.chunk < 0 or a.flow_cap < 0:
         raise SystemExit("--chunk / --flow-cap: want a positive count")
-    if not a.filter:
+    if not a.filter and a.stream is None:
         raise SystemExit("--filter: want at least one (without a filter every packet passes: copy the file)")
     filters = [parse_filter(f) for f in a.filter]
+    blob = None
+    if a.stream is not None:
+        try:
+            blob, _ = abi.flow_stream_compile(a.stream)
+        except abi.BtError as e:   # never a silent per-packet match instead
+            raise SystemExit(f"pcap_sessions: --stream: {e}")
     data = np.fromfile(a.src, np.uint8)
     try:
         info, desc = abi.pcap_index(data)
@@ -81,7 +96,7 @@ def main():
     ctx = abi.Context(a.device)
     fh, whole = None, False
     try:
-        if any(s.kind == K_HOST for s in ctx.compile(filters)):
+        if filters and any(s.kind == K_HOST for s in ctx.compile(filters)):
             raise SystemExit("pcap_sessions: a filter the GPU cannot decide (a CUSTOM callback, a PAYLOAD regex outside "
                              "its subset) is in the program")
         lay = abi.flow_track_layout(cap)
@@ -95,6 +110,14 @@ def main():
         d_sel, d_sres = ctx.alloc(max(16, (max_n + 63) // 64 * 8)), ctx.alloc(32)
         d_pack, d_tot, d_np = ctx.alloc(max_bytes + LEAD * max_n + 256), ctx.alloc(8), ctx.alloc(8)
         bufs = [d_state, d_scratch, d_res, d_marks, d_ids, d_ver, d_mres, d_data, d_desc, d_sel, d_sres, d_pack, d_tot, d_np]
+        if blob is not None:
+            sneed = abi.flow_stream_scratch_bytes(max_n, cap)
+            d_blob, d_stab, d_sscr = ctx.alloc(len(blob)), ctx.alloc(32 * cap), ctx.alloc(max(256, sneed))
+            d_hit = ctx.alloc(max(16, (max_n + 63) // 64 * 8)) if filters else None   # beside the verdict, or in its place
+            d_stres, d_mres2 = ctx.alloc(max(64, 64 * len(parts))), ctx.alloc(max(32, 32 * len(parts)))
+            bufs += [b for b in (d_blob, d_stab, d_sscr, d_hit, d_stres, d_mres2) if b is not None]
+            d_blob.upload(blob)
+            d_stab.zero()
         d_marks.zero()
         ctx.reserve(max_n)
         ctx.flow_track_init(d_state, lay["total"], cap, flags)
@@ -110,9 +133,15 @@ def main():
         for k, (lo, hi) in enumerate(parts):   # pass one: the marks
             batch = stage(lo, hi)
             ver, ids = d_ver.ptr + 8 * int(word0[k]), d_ids.ptr + 4 * lo
-            ctx.run_device(batch, abi.Outputs(None, 0, ver, None, None, None))
+            if filters:
+                ctx.run_device(batch, abi.Outputs(None, 0, ver, None, None, None))
             ctx.flow_track_update(d_state, batch, d_scratch, need, d_res, flow_id=ids)
-            ctx.flow_mark_update(batch, ids, ver, MARK, d_marks, cap, d_mres.ptr + 32 * k)
+            if blob is not None:
+                hit = d_hit.ptr if filters else ver
+                ctx.flow_stream(batch, ids, None, flags, blob, d_blob, d_stab, cap, d_sscr, sneed, d_stres.ptr + 64 * k, hit=hit)
+                ctx.flow_mark_update(batch, ids, hit, MARK, d_marks, cap, (d_mres2 if filters else d_mres).ptr + 32 * k)
+            if filters:
+                ctx.flow_mark_update(batch, ids, ver, MARK, d_marks, cap, d_mres.ptr + 32 * k)
         ctx.synchronize()
         hdr = abi.FlowTrackHdr.from_bytes(d_state.download(np.zeros(128, np.uint8))).as_dict()
         if hdr["overflow_packets"]:
@@ -127,6 +156,18 @@ def main():
                 out["hit_packets"] += r["hit_packets"]
                 out["marked_flows"] += r["new_marked_flows"]
                 out["unkeyed_hits"] += r["unkeyed_hits"]
+            if blob is not None:
+                raw, raw2 = d_stres.download(np.zeros(64 * len(parts), np.uint8)), d_mres2.download(np.zeros(32 * len(parts), np.uint8))
+                out.update(stream_packets=0, stream_bytes=0, stream_hit_packets=0)
+                for k in range(len(parts)):
+                    r = abi.FlowStreamResult.from_bytes(raw[64 * k:64 * k + 64]).as_dict()
+                    if r["bad_ids"]:
+                        raise SystemExit("pcap_sessions: the tracker's flow ids do not fit the stream table")
+                    out["stream_packets"] += r["stream_packets"]
+                    out["stream_bytes"] += r["stream_bytes"]
+                    out["stream_hit_packets"] += r["hit_packets"]
+                    if filters:   # the flows the stream's hits marked first
+                        out["marked_flows"] += abi.FlowMarkResult.from_bytes(raw2[32 * k:32 * k + 32]).as_dict()["new_marked_flows"]
         if a.invert and parts:   # base = the packets that did not pass
             words = d_ver.download(np.zeros(8 * int(word0[-1]), np.uint8)).view(np.uint64)
             d_ver.upload(~words)
