@@ -866,6 +866,83 @@ def decode_flow_stream(rec) -> dict:
             "hit": bool(int(r["hit_packets"][0]) or int(r["hit_packets"][1]))}
 
 
+# bt_flow_tcpseq_*: a segment's class against its direction's sequence space, and "not classified" in off
+TCPSEQ_NONE, TCPSEQ_FIRST, TCPSEQ_IN_ORDER, TCPSEQ_GAP, TCPSEQ_OLD, TCPSEQ_OVERLAP = range(6)
+TCPSEQ_NAMES = ("none", "first", "in_order", "gap", "old", "overlap")
+TCPSEQ_OFF_NONE = -(1 << 63)
+
+# numpy views of bt_flow_tcpseq_dir (64 B) and bt_flow_tcpseq_rec (128 B, one per direction): record f belongs to flow number f
+FlowTcpseqDir = np.dtype({"names": ["pos", "hi", "last_seq", "have", "seq_packets", "old_packets", "gap_packets", "overlap_packets",
+                                    "old_bytes", "gap_bytes", "reserved"],
+                          "formats": ["<i8", "<i8", "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u8", "<u8", "<u8"],
+                          "offsets": [0, 8, 16, 20, 24, 28, 32, 36, 40, 48, 56], "itemsize": 64})
+FlowTcpseqRec = np.dtype({"names": ["d"], "formats": [(FlowTcpseqDir, 2)], "offsets": [0], "itemsize": 128})
+
+
+class FlowTcpseqOut(ctypes.Structure):
+    """bt_flow_tcpseq_out (48 B): the optional class bytes, offsets and selection words, and the result."""
+    _fields_ = [("cls", ctypes.c_void_p), ("off", ctypes.c_void_p), ("out_select", ctypes.c_void_p), ("result", ctypes.c_void_p),
+                ("reserved", ctypes.c_uint64 * 2)]
+
+
+class FlowTcpseqResult(_Counts):
+    """bt_flow_tcpseq_result (64 B): the counts of a TCP sequence classification call."""
+    _fields_ = [("n", ctypes.c_uint32), ("selected", ctypes.c_uint32), ("seq_packets", ctypes.c_uint32), ("first", ctypes.c_uint32),
+                ("in_order", ctypes.c_uint32), ("gap", ctypes.c_uint32), ("old", ctypes.c_uint32), ("overlap", ctypes.c_uint32),
+                ("unkeyed", ctypes.c_uint32), ("bad_ids", ctypes.c_uint32), ("seq_bytes", ctypes.c_uint64),
+                ("old_bytes", ctypes.c_uint64), ("gap_bytes", ctypes.c_uint64)]
+
+
+def flow_tcpseq_scratch_bytes(n: int, flow_cap: int) -> int:
+    """bt_flow_tcpseq_scratch_bytes (host only)."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_tcpseq_scratch_bytes(n, flow_cap, ctypes.byref(b)))
+    return b.value
+
+
+def flow_tcpseq_host(data, desc, flow_id, select, table_flags: int, table: np.ndarray, cls=None, off=None, out_select=None,
+                     nbytes=None) -> dict:
+    """bt_flow_tcpseq_host (host only): the TCP segments of the frames desc (packed descriptors) lists
+    in `data` whose bit is set in `select` (verdict-layout u64 words, None = all) and whose flow
+    number flow_id[i] is below len(table) are placed in their (flow, direction) sequence space and
+    classified against `table` (FlowTcpseqRec, in place). cls (n u8), off (n i8) and out_select
+    (ceil(n/64) u64 words, may be `select`: select & ~OLD) are optional. Returns the result dict."""
+    a = _byte_view(data)
+    keep = a if len(a) else np.zeros(1, np.uint8)
+    d = np.ascontiguousarray(desc, np.uint64)
+    n = len(d)
+    nw = (n + 63) // 64
+    ids = np.ascontiguousarray(flow_id, np.uint32)
+    for arr in (select, out_select):
+        if arr is not None and (arr.dtype != np.uint64 or not arr.flags["C_CONTIGUOUS"] or len(arr) < nw):
+            raise ValueError("flow_tcpseq_host: ceil(n/64) contiguous u64 words for select and out_select")
+    if cls is not None and (cls.dtype != np.uint8 or not cls.flags["C_CONTIGUOUS"] or len(cls) < n):
+        raise ValueError("flow_tcpseq_host: n contiguous u8 for cls")
+    if off is not None and (off.dtype != np.int64 or not off.flags["C_CONTIGUOUS"] or len(off) < n):
+        raise ValueError("flow_tcpseq_host: n contiguous i8 for off")
+    if len(ids) != n or table.dtype != FlowTcpseqRec or not table.flags["C_CONTIGUOUS"]:
+        raise ValueError("flow_tcpseq_host: one flow_id per descriptor and a contiguous FlowTcpseqRec table")
+    at = lambda x: x.ctypes.data if x is not None and len(x) else None  # noqa: E731
+    res = FlowTcpseqResult()
+    out = FlowTcpseqOut(at(cls), at(off), at(out_select), ctypes.addressof(res), (ctypes.c_uint64 * 2)(0, 0))
+    _check(lib().bt_flow_tcpseq_host(keep.ctypes.data, len(a) if nbytes is None else nbytes, at(d), n, at(ids), at(select),
+                                     table_flags, at(table), len(table), ctypes.byref(out)))
+    return res.as_dict()
+
+
+def decode_flow_tcpseq(rec) -> dict:
+    """One FlowTcpseqRec in plain values, per direction: whether the direction was seen, its last
+    packet's offset and sequence number, the highest offset seen, and the packets and bytes that
+    were old (retransmitted or late), ahead of a gap or overlapping."""
+    r = np.ascontiguousarray(rec, FlowTcpseqRec).reshape(1)[0]
+    names = ("seq_packets", "old_packets", "gap_packets", "overlap_packets", "old_bytes", "gap_bytes")
+    out = {"have": [bool(int(r["d"][k]["have"])) for k in range(2)], "pos": [int(r["d"][k]["pos"]) for k in range(2)],
+           "hi": [int(r["d"][k]["hi"]) for k in range(2)], "last_seq": [int(r["d"][k]["last_seq"]) for k in range(2)]}
+    for name in names:
+        out[name] = [int(r["d"][k][name]) for k in range(2)]
+    return out
+
+
 # bt_flow_track_top_*: the metric a top-K query orders by, and its limit on k
 FLOW_TOP_BYTES, FLOW_TOP_PACKETS, FLOW_TOP_DURATION, FLOW_TOP_TCP_SYN, FLOW_TOP_TCP_RST = range(5)
 FLOW_TOP_MAX_K = 4096
@@ -1096,6 +1173,7 @@ EXPORTS = [
     "bt_flow_seq_scratch_bytes", "bt_flow_seq_device", "bt_flow_seq_host", "bt_time_flow_seq",
     "bt_flow_stream_compile", "bt_flow_stream_scratch_bytes", "bt_flow_stream_device", "bt_flow_stream_host",
     "bt_time_flow_stream",
+    "bt_flow_tcpseq_scratch_bytes", "bt_flow_tcpseq_device", "bt_flow_tcpseq_host", "bt_time_flow_tcpseq",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -1211,6 +1289,12 @@ def lib() -> ctypes.CDLL:
                                                ctypes.POINTER(FlowStreamOut)]),
         "bt_time_flow_stream": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, u32, vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
                                                ctypes.POINTER(FlowStreamOut), u32, vp, vp]),
+        "bt_flow_tcpseq_scratch_bytes": (ctypes.c_int, [u32, u32, ctypes.POINTER(ctypes.c_uint64)]),
+        "bt_flow_tcpseq_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
+                                                 ctypes.POINTER(FlowTcpseqOut), vp]),
+        "bt_flow_tcpseq_host": (ctypes.c_int, [vp, ctypes.c_uint64, vp, u32, vp, vp, u32, vp, u32, ctypes.POINTER(FlowTcpseqOut)]),
+        "bt_time_flow_tcpseq": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
+                                               ctypes.POINTER(FlowTcpseqOut), u32, vp, vp]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -1713,7 +1797,25 @@ class Context:
                                            pat.ctypes.data if len(pat) else None, ptr(pattern_device), len(pat), ptr(table), flow_cap,
                                            ptr(scratch), scratch_bytes, ctypes.byref(out), stream))
 
+    def flow_tcpseq(self, batch: Batch, flow_id, select, table_flags: int, table, flow_cap: int, scratch, scratch_bytes: int, result,
+                    cls=None, off=None, out_select=None, stream=None):
+        """bt_flow_tcpseq_device: the TCP segments of the packets of `batch` whose bit is set in `select`
+        (verdict-layout words on the device; None = all) and whose flow number flow_id[i] is below
+        flow_cap are placed in their (flow, direction) sequence space and classified (TCPSEQ_*)
+        against `table` (flow_cap FlowTcpseqRec on the device, zeroed once by the caller). cls (n
+        bytes), off (n int64) and out_select (ceil(n/64) u64 words, may be `select`: select & ~OLD,
+        the selection to hand to flow_stream) are optional. scratch: flow_tcpseq_scratch_bytes(n,
+        flow_cap) bytes, 256-byte aligned. result: 64 B (FlowTcpseqResult), 8-byte aligned. Pointers
+        are addresses or DeviceBuffers. Asynchronous on `stream`: enqueue it behind the calls that
+        wrote flow_id and select."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        out = FlowTcpseqOut(ptr(cls), ptr(off), ptr(out_select), ptr(result), (ctypes.c_uint64 * 2)(0, 0))
+        _check(lib().bt_flow_tcpseq_device(self.h, ctypes.byref(batch), ptr(flow_id), ptr(select), table_flags, ptr(table), flow_cap,
+                                           ptr(scratch), scratch_bytes, ctypes.byref(out), stream))
+
     # the host-only forms beside their device forms
+    flow_tcpseq_host = staticmethod(flow_tcpseq_host)
+    flow_tcpseq_scratch_bytes = staticmethod(flow_tcpseq_scratch_bytes)
     flow_stream_host = staticmethod(flow_stream_host)
     flow_stream_compile = staticmethod(flow_stream_compile)
     flow_stream_scratch_bytes = staticmethod(flow_stream_scratch_bytes)

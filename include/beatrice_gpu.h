@@ -95,7 +95,8 @@ extern "C" {
  * bt_flow_track_side_move_host, bt_flow_mark_update_device, bt_flow_mark_update_host,
  * bt_flow_mark_select_device, bt_flow_mark_select_host, bt_flow_seq_scratch_bytes,
  * bt_flow_seq_device, bt_flow_seq_host, bt_flow_stream_compile, bt_flow_stream_scratch_bytes,
- * bt_flow_stream_device, bt_flow_stream_host. */
+ * bt_flow_stream_device, bt_flow_stream_host, bt_flow_tcpseq_scratch_bytes, bt_flow_tcpseq_device,
+ * bt_flow_tcpseq_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -1122,7 +1123,8 @@ int  bt_flow_seq_host(const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_
  * one, in this batch or in an earlier call.
  * The stream of (flow f, direction d) is the concatenation, in packet order within a batch and in
  * call order across batches, of the L4 payloads of its contributing packets. It is arrival order,
- * not TCP sequence order: retransmissions and reordering are not undone.
+ * not TCP sequence order: retransmissions and reordering are not undone (bt_flow_tcpseq_device in
+ * front of this call gives a `select` without the retransmits).
  * Packet i contributes when its bit is set in `select` (verdict-word layout, NULL = every packet in
  * [0, n); bits at or above n are ignored), flow_id[i] < flow_cap, the walk of bt_flow_fanout_device
  * finds a whole TCP or UDP header under the flow key's rule (the statistics table's BT_FSEEN_L4
@@ -1191,6 +1193,96 @@ int  bt_flow_stream_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* 
 int  bt_flow_stream_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_id,
                          const uint64_t* select, uint32_t table_flags, const void* pattern, uint32_t pattern_bytes,
                          bt_flow_stream_rec* table, uint32_t flow_cap, const bt_flow_stream_out* out);
+
+/* ---- per-flow TCP sequence classification: retransmits, gaps, order -----------------------
+ * The sequence primitive numbers a flow's packets and the stream matcher concatenates their
+ * payloads, both in arrival order. This primitive reads the TCP sequence numbers: every segment
+ * of a (flow, direction) is placed in that direction's sequence space and classified against the
+ * highest byte seen so far.
+ * Packet i participates when its bit is set in `select` (verdict-word layout, NULL = every packet
+ * in [0, n); bits at or above n are ignored), flow_id[i] < flow_cap, the walk of
+ * bt_flow_fanout_device finds a whole TCP header under the statistics table's BT_FSEEN_L4 rule
+ * (protocol 6, the 20 header bytes in the frame, IPv4 neither MF nor a fragment offset) and its
+ * sequence length L is > 0. L comes from header fields only, as the statistics table's payload
+ * (a snapped capture still advances): plen = max(0, ip_payload - 4 (tcp[12] >> 4)) in signed
+ * 32-bit arithmetic, L = plen + SYN + FIN; RST adds nothing. A pure ACK or a zero-length
+ * keep-alive has L = 0: it does not participate, its class is BT_TCPSEQ_NONE and its record is
+ * untouched. s is the big-endian 32 bits at tcp[4 .. 8); the direction d is the TCP side table's
+ * under table_flags (0 without BT_FLOWTAB_BIDIRECTIONAL). Frame bytes are read under the
+ * fan-out's read rule: a byte at or past `bytes` reads as zero. A BT_FLOW_ID_* sentinel
+ * contributes nothing; any other selected id >= flow_cap counts in bad_ids.
+ * The record of (flow, direction) holds have, last_seq (the s of the last participating packet),
+ * pos (that packet's unwrapped start, int64) and hi (the highest unwrapped end seen, int64).
+ * Packets are taken in packet order within a batch and in call order across batches:
+ *   the first packet of a direction: u = 0, class FIRST, hi = L;
+ *   otherwise u = pos + (int64)(int32)(s - last_seq), e = u + L; the class against hi, then hi =
+ *   max(hi, e):
+ *     IN_ORDER  u == hi;
+ *     GAP       u > hi: the segment lies ahead of everything seen; gap_bytes += u - hi;
+ *     OLD       u < hi and e <= hi: every byte at or below the highest seen; old_bytes += L;
+ *     OVERLAP   u < hi < e; old_bytes += hi - u;
+ *   after every participating packet pos = u, last_seq = s.
+ * Unwrapping is against the previous packet, so the 2^32 wrap is followed for any flow length, as
+ * long as consecutive participating packets of a direction lie within 2^31 of each other (a step
+ * of exactly 0x80000000 is taken as -2^31). Behaviour is defined while |u| < 2^63, which cannot be
+ * left in fewer than 2^32 packets of one direction.
+ * OLD means "retransmitted or late": the table keeps no hole list, so a segment that fills a hole
+ * behind a GAP is OLD as well. In a direction whose gap_packets is 0 every OLD packet is a certain
+ * duplicate. A reused 5-tuple with a new ISN shows as one large GAP or OLD until the tracker's
+ * expire zeroes the record.
+ * table: flow_cap records bt_flow_tcpseq_rec (128 B, two bt_flow_tcpseq_dir) of the caller's
+ * memory, 8-byte aligned, zeroed once (all-zero = nothing seen); counts mod 2^32, bytes mod 2^64.
+ * It goes through an expire by bt_flow_track_side_move_device with rec_bytes = 128; there is no
+ * expire call of its own.
+ * Outputs, each optional: out->cls, n bytes, the class; out->off, n int64, the unwrapped start u
+ * (the packet's offset in its direction's sequence space), BT_TCPSEQ_OFF_NONE for a packet that
+ * is not classified; out->out_select (verdict layout, ceil(n/64) words) = select & ~OLD: a
+ * selected packet that does not participate stays selected, bits at or above n are written as 0,
+ * out_select == select is allowed, in place. It is the selection to hand to bt_flow_stream_device
+ * so that a retransmit does not enter a stream twice.
+ * *out->result: selected = the select bits in [0, n); seq_packets, seq_bytes = the participating
+ * packets and the sum of their L; first .. overlap = the packets of each class; old_bytes,
+ * gap_bytes as above; unkeyed = the selected packets with a sentinel id; bad_ids as above.
+ * Asynchronous on `stream` (NULL = the context's), behind the call that wrote flow_id; no
+ * allocation, no host synchronisation; n == 0 writes *result in stream order and nothing else.
+ * scratch: bt_flow_tcpseq_scratch_bytes(n, flow_cap) bytes of device memory, 256-byte aligned; the
+ * call initialises what it reads. flow_cap <= 2^31. Nothing is written outside table[0 ..
+ * flow_cap), the requested outputs, the scratch and *out->result; every output is exact, equal to
+ * the host form's and bit-identical from run to run.
+ * BT_E_INVALID_ARGUMENT before the context or any HIP call: a null frames, out or out->result; a
+ * null flow_id (with n > 0) or table (with flow_cap > 0); misalignment (flow_id 4 bytes; table,
+ * select, off, out_select, result 8; scratch 256); unknown table_flags; a non-zero reserved; a
+ * BT_BATCH_PREFIXES / BT_BATCH_LEAN batch; flow_cap above 2^31; a scratch that is too small; then
+ * a null context.
+ * bt_flow_tcpseq_host: the same on the calling thread as a plain loop, which is the definition;
+ * no context, no device and no scratch; packed descriptors. */
+enum { BT_TCPSEQ_NONE = 0, BT_TCPSEQ_FIRST = 1, BT_TCPSEQ_IN_ORDER = 2, BT_TCPSEQ_GAP = 3, BT_TCPSEQ_OLD = 4,
+       BT_TCPSEQ_OVERLAP = 5 };
+#define BT_TCPSEQ_OFF_NONE INT64_MIN
+typedef struct bt_flow_tcpseq_dir {            /* 64 B; all-zero = nothing seen */
+    int64_t  pos, hi;                          /* the last packet's unwrapped start; the highest unwrapped end seen */
+    uint32_t last_seq, have;
+    uint32_t seq_packets, old_packets, gap_packets, overlap_packets;
+    uint64_t old_bytes, gap_bytes, reserved;
+} bt_flow_tcpseq_dir;
+typedef struct bt_flow_tcpseq_rec { bt_flow_tcpseq_dir d[2]; } bt_flow_tcpseq_rec;   /* 128 B, per direction */
+typedef struct bt_flow_tcpseq_out {
+    uint8_t* cls; int64_t* off; uint64_t* out_select;
+    struct bt_flow_tcpseq_result* result;
+    uint64_t reserved[2];
+} bt_flow_tcpseq_out;
+typedef struct bt_flow_tcpseq_result {         /* 64 B, device-visible, 8-byte aligned */
+    uint32_t n, selected, seq_packets, first, in_order, gap, old, overlap, unkeyed, bad_ids;
+    uint64_t seq_bytes, old_bytes, gap_bytes;
+} bt_flow_tcpseq_result;
+
+int  bt_flow_tcpseq_scratch_bytes(uint32_t n, uint32_t flow_cap, uint64_t* bytes);    /* host only */
+int  bt_flow_tcpseq_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id /* device, n */,
+                           const uint64_t* select /* NULL = all n */, uint32_t table_flags, bt_flow_tcpseq_rec* table,
+                           uint32_t flow_cap, void* scratch, uint64_t scratch_bytes, const bt_flow_tcpseq_out* out, void* stream);
+int  bt_flow_tcpseq_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_id,
+                         const uint64_t* select, uint32_t table_flags, bt_flow_tcpseq_rec* table, uint32_t flow_cap,
+                         const bt_flow_tcpseq_out* out);
 
 /* ---- top-K flows of a tracker: the largest flows by a measure, selected on the device ------
  * bt_flow_track_top_device: the k largest flows of the tracker at `state` by opts->metric,

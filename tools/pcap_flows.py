@@ -5,7 +5,7 @@ the file (the NetFlow / conntrack view of a capture).
 Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [--bidirectional] [--l3-only]
                                   [--top N] [--format csv|json] [--chunk-packets N]
                                   [--track [--idle SECONDS] [--flow-cap N] [--tcp [--closed-idle SECONDS]]
-                                           [--stats] [--by bytes|packets|duration|syn|rst]
+                                           [--stats] [--seq] [--by bytes|packets|duration|syn|rst]
                                            [--hosts [--top N --by bytes|packets|flows]]]
   --filter         as tools/pcap_filter.py takes it; only passing packets are counted
   --bidirectional  both directions of a conversation are one flow (BT_FLOWTAB_BIDIRECTIONAL): the
@@ -39,6 +39,12 @@ Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [-
                    rtt_client (SYN-ACK to ACK) in the capture's time unit (micro- or nanoseconds), empty where the
                    handshake was not seen. With --idle the statistics of a flow that ages out leave with it
                    (bt_flow_track_side_move_device behind the expire). Not with --top or --hosts.
+  --seq            with --track: a TCP sequence side table beside the tracker (bt_flow_tcpseq_device behind every
+                   update). Adds per direction (the second with the suffix _rev) seq_packets (segments that take
+                   sequence space), old_packets (retransmitted or late: every byte at or below the highest seen; with
+                   gap_packets 0 certain duplicates), gap_packets (ahead of everything seen: a loss or reordering in
+                   front), overlap_packets, old_bytes and gap_bytes. With --idle the record of a flow that ages out
+                   leaves with it. Not with --top or --hosts.
   --by MEASURE     with --track and --top N, N <= 4096: what the top is ordered by, largest first and the
                    earliest-seen flow first among equals: bytes (default), packets (both directions), duration
                    (last minus first packet time by the pcap record headers), syn or rst (with --tcp: packets with
@@ -83,6 +89,8 @@ TCP_COLUMNS = ("tcp_flags_fwd", "tcp_flags_rev", "tcp_state", "syn", "fin", "rst
 STAT_DIR_COLUMNS = ("len_min", "len_mean", "len_max", "len_stddev", "ttl_min", "ttl_max", "payload_bytes", "payload_packets")
 STAT_COLUMNS = ("protocols", "proto_max") + STAT_DIR_COLUMNS + tuple(c + "_rev" for c in STAT_DIR_COLUMNS)
 RTT_COLUMNS = ("initiator", "rtt_server", "rtt_client")
+SEQ_DIR_COLUMNS = ("seq_packets", "old_packets", "gap_packets", "overlap_packets", "old_bytes", "gap_bytes")
+SEQ_COLUMNS = SEQ_DIR_COLUMNS + tuple(c + "_rev" for c in SEQ_DIR_COLUMNS)
 U64_MAX = (1 << 64) - 1
 HOST_COLUMNS = ("address", "flows_src", "flows_dst", "packets_sent", "bytes_sent", "packets_received", "bytes_received",
                 "first_seen", "last_seen")
@@ -139,6 +147,14 @@ def describe_stats(r: dict, rec, packets, nbytes, bidirectional: bool):
         r["rtt_client"] = t["rtt_client"] if t["client_valid"] else None
 
 
+def describe_seq(r: dict, rec):
+    """The --seq columns of one output line from a bt_flow_tcpseq_rec."""
+    d = abi.decode_flow_tcpseq(rec)
+    for k, suffix in enumerate(("", "_rev")):
+        for c in SEQ_DIR_COLUMNS:
+            r[c + suffix] = d[c][k]
+
+
 def merge(table: dict, flows: np.ndarray, lo: int):
     """Add one chunk's records (packet numbers relative to `lo`) to the file's table."""
     for f in flows:
@@ -172,7 +188,7 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         ts = word(0) * np.uint64(unit) + word(4)
     rows = []
 
-    def lines(recs, side=None, stat=None):
+    def lines(recs, side=None, stat=None, seq=None):
         for k, f in enumerate(recs):
             v = [int(f["packets"][0]), int(f["packets"][1]), int(f["bytes"][0]), int(f["bytes"][1]),
                  int(starts[f["first_batch"]]) + int(f["first"]), int(starts[f["last_batch"]]) + int(f["last"])]
@@ -188,6 +204,8 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
                 r["syn"], r["fin"], r["rst"] = int(t["syn_packets"]), int(t["fin_packets"]), int(t["rst_packets"])
             if stat is not None:
                 describe_stats(r, stat[k], v[0:2], v[2:4], bool(flags & abi.FLOWTAB_BIDIRECTIONAL))
+            if seq is not None:
+                describe_seq(r, seq[k])
             rows.append(r)
 
     if a.tcp and timed:
@@ -199,17 +217,29 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
     if timed:
         d_ts, d_xscratch, d_xres, d_exp = ctx.alloc(max(16, max_n * 8)), ctx.alloc(xneed), ctx.alloc(32), ctx.alloc(104 * cap)
         bufs += [d_ts, d_xscratch, d_xres, d_exp]
-    if a.tcp or a.stats:   # the update's flow ids feed the side tables
+    sided = a.stats or a.seq   # side tables that follow an expire's remap
+    if a.tcp or sided:   # the update's flow ids feed the side tables
         d_ids = ctx.alloc(max(16, max_n * 4))
         bufs.append(d_ids)
+    if sided and timed:
+        mneed = abi.flow_track_side_move_scratch_bytes(cap, 128)
+        d_remap, d_mscratch = ctx.alloc(4 * cap), ctx.alloc(mneed)
+        bufs += [d_remap, d_mscratch]
     if a.stats:   # the statistics, zeroed once; with --idle they follow the expire's remap
         d_stat, d_sres = ctx.alloc(128 * cap), ctx.alloc(32)
         d_stat.zero()
         bufs += [d_stat, d_sres]
         if timed:
-            mneed = abi.flow_track_side_move_scratch_bytes(cap, 128)
-            d_remap, d_mscratch, d_exp_stat = ctx.alloc(4 * cap), ctx.alloc(mneed), ctx.alloc(128 * cap)
-            bufs += [d_remap, d_mscratch, d_exp_stat]
+            d_exp_stat = ctx.alloc(128 * cap)
+            bufs.append(d_exp_stat)
+    if a.seq:   # the sequence spaces, zeroed once; with --idle they follow the expire's remap
+        qneed = abi.flow_tcpseq_scratch_bytes(max_n, cap)
+        d_seq, d_qscratch, d_qres = ctx.alloc(128 * cap), ctx.alloc(max(256, qneed)), ctx.alloc(64)
+        d_seq.zero()
+        bufs += [d_seq, d_qscratch, d_qres]
+        if timed:
+            d_exp_seq = ctx.alloc(128 * cap)
+            bufs.append(d_exp_seq)
     if a.tcp:   # the side table, zeroed once
         d_tcp, d_tres = ctx.alloc(16 * cap), ctx.alloc(32)
         d_tcp.zero()
@@ -242,26 +272,31 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         if filters:
             ctx.run_device(batch, abi.Outputs(None, 0, d_ver.ptr, None, None, None))
         ctx.flow_track_update(d_state, batch, d_scratch, need, d_res, select=d_ver if filters else None,
-                              ts=d_ts if stamped else None, flow_id=d_ids if a.tcp or a.stats else None)
+                              ts=d_ts if stamped else None, flow_id=d_ids if a.tcp or sided else None)
         if a.tcp:
             ctx.flow_tcp_update(batch, d_ids, flags, d_tcp, cap, d_tres)
         if a.stats:
             ctx.flow_stat_update(batch, d_ids, flags, d_stat, cap, d_sres, ts=d_ts)
+        if a.seq:   # unselected packets carry the UNSELECTED sentinel: they are in no sequence space
+            ctx.flow_tcpseq(batch, d_ids, None, flags, d_seq, cap, d_qscratch, qneed, d_qres)
         if timed:   # what aged out is printed now: its count and records come back, nothing else
             if a.tcp:
                 ctx.flow_track_expire_tcp(d_state, int(ts[hi - 1]), int(a.idle * unit), closed, d_tcp, d_xscratch, xneed, d_xres,
-                                          expired=d_exp, expired_cap=cap, expired_tcp=d_exp_tcp, remap=d_remap if a.stats else None)
+                                          expired=d_exp, expired_cap=cap, expired_tcp=d_exp_tcp, remap=d_remap if sided else None)
             else:
                 ctx.flow_track_expire(d_state, int(ts[hi - 1]), int(a.idle * unit), d_xscratch, xneed, d_xres, expired=d_exp, expired_cap=cap,
-                                      remap=d_remap if a.stats else None)
+                                      remap=d_remap if sided else None)
             if a.stats:   # the statistics of the flows that stay move up, those of the flows that leave come out
                 ctx.flow_track_side_move(d_stat, 128, cap, d_remap, d_xres, d_mscratch, mneed, expired_side=d_exp_stat, expired_cap=cap)
+            if a.seq:   # and so do the sequence spaces
+                ctx.flow_track_side_move(d_seq, 128, cap, d_remap, d_xres, d_mscratch, mneed, expired_side=d_exp_seq, expired_cap=cap)
             ctx.synchronize()
             x = abi.FlowTrackExpireResult.from_bytes(d_xres.download(np.zeros(32, np.uint8))).as_dict()
             if x["n_expired"]:
                 lines(d_exp.download(np.zeros(104 * x["n_expired"], np.uint8)).view(abi.FlowTrackRec),
                       d_exp_tcp.download(np.zeros(16 * x["n_expired"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None,
-                      d_exp_stat.download(np.zeros(128 * x["n_expired"], np.uint8)).view(abi.FlowStatRec) if a.stats else None)
+                      d_exp_stat.download(np.zeros(128 * x["n_expired"], np.uint8)).view(abi.FlowStatRec) if a.stats else None,
+                      d_exp_seq.download(np.zeros(128 * x["n_expired"], np.uint8)).view(abi.FlowTcpseqRec) if a.seq else None)
     if on_device:   # behind the last update and side table update, on their stream
         ctx.flow_track_top(d_state, TOP_BY[a.by], a.top, d_tscratch, tneed, d_top_res, top=d_top, tcp=d_tcp if a.tcp else None,
                            top_tcp=d_top_tcp if a.tcp else None)
@@ -293,7 +328,8 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         both = d_state.download(np.zeros(lay["records"] + 104 * hdr["n_flows"], np.uint8))
         lines(both[lay["records"]:].view(abi.FlowTrackRec),
               d_tcp.download(np.zeros(16 * hdr["n_flows"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None,
-              d_stat.download(np.zeros(128 * hdr["n_flows"], np.uint8)).view(abi.FlowStatRec) if a.stats else None)
+              d_stat.download(np.zeros(128 * hdr["n_flows"], np.uint8)).view(abi.FlowStatRec) if a.stats else None,
+              d_seq.download(np.zeros(128 * hdr["n_flows"], np.uint8)).view(abi.FlowTcpseqRec) if a.seq else None)
     totals["selected"], totals["no_key"] = hdr["selected_packets"], hdr["none_packets"]
     abi.Context.flow_track_forget(d_state)   # before its memory goes back
     for b in bufs:
@@ -348,6 +384,7 @@ def main():
     ap.add_argument("--by", choices=tuple(TOP_BY) + ("flows",), default=None)
     ap.add_argument("--hosts", action="store_true")
     ap.add_argument("--stats", action="store_true")
+    ap.add_argument("--seq", action="store_true")
     a = ap.parse_args()
     if a.chunk_packets < 0 or a.top < 0:
         raise SystemExit("--chunk-packets / --top: want a positive count")
@@ -363,6 +400,8 @@ def main():
         raise SystemExit("--flow-cap: want a positive count")
     if a.stats and (not a.track or a.top or a.hosts):
         raise SystemExit("--stats: only with --track, and without --top and --hosts")
+    if a.seq and (not a.track or a.top or a.hosts):
+        raise SystemExit("--seq: only with --track, and without --top and --hosts")
     if a.hosts and (not a.track or a.idle is not None):
         raise SystemExit("--hosts: only with --track, and without --idle")
     if a.hosts and a.by is not None and (a.by not in HOSTS_BY or not a.top):
@@ -405,6 +444,8 @@ def main():
     columns = COLUMNS + (("first_ts", "last_ts") if a.idle is not None else ()) + (TCP_COLUMNS if a.tcp else ())
     if a.stats:
         columns += STAT_COLUMNS + (RTT_COLUMNS if a.bidirectional else ())
+    if a.seq:
+        columns += SEQ_COLUMNS
     if a.hosts:   # host records in order of first appearance; a top is sorted here (stable: ties stay in that order)
         columns = HOST_COLUMNS + (HOST_TCP_COLUMNS if a.tcp else ())
         if a.top:

@@ -2,12 +2,16 @@
 --invert, drop those connections whole): the session view of tools/pcap_filter.py, decided on the GPU.
 
 Usage: python tools/pcap_sessions.py --in a.pcap --out b.pcap --filter TYPE:EXPR[:PRIO] ...
-                                     [--stream EXPR] [--bidirectional] [--l3-only] [--invert] [--flow-cap N] [--chunk PACKETS]
+                                     [--stream EXPR [--skip-retransmits]] [--bidirectional] [--l3-only] [--invert]
+                                     [--flow-cap N] [--chunk PACKETS]
   --filter         as tools/pcap_filter.py takes it
   --stream EXPR    also (or, without --filter, only) select the connections in whose payload stream EXPR matches,
                    wherever the match lies: across TCP segments and past a packet's first 100 bytes
                    (bt_flow_stream_device, per direction, in arrival order). EXPR must have bounded memory: no +, *,
                    {n,}, ^, $ or \\b; anything else ends the run with the construct's name, never a per-packet match
+  --skip-retransmits  with --stream: classify the TCP segments first (bt_flow_tcpseq_device) and keep those whose bytes
+                   all lie at or below the highest sequence number seen (retransmitted or late) out of the stream, so
+                   that HE, LL, LL again, O reads HELLO and not HELLLLO
   --bidirectional  both directions of a conversation are one session (BT_FLOWTAB_BIDIRECTIONAL)
   --l3-only        never key on ports (BT_FLOWTAB_L3_ONLY): a session is a pair of addresses
   --invert         write the complement: every packet that is in no session with a passing packet
@@ -32,7 +36,7 @@ With --stream, pass one per chunk is: the filter (if any), the tracker update, b
 against one stream table for the whole file, bt_flow_mark_update_device with the stream's hits (and, with a filter, a
 second one with the verdict), then pass two as above; without a filter the stream's hit words stand where the verdict's do.
 Prints one JSON line: packets, hit_packets, flows, marked_flows, unkeyed_hits, written_packets, written_bytes, and with
---stream also stream_packets, stream_bytes, stream_hit_packets.
+--stream also stream_packets, stream_bytes, stream_hit_packets, and with --skip-retransmits seq_packets and old_packets.
 """
 from __future__ import annotations
 
@@ -61,6 +65,7 @@ def main():
     ap.add_argument("--out", dest="dst", required=True)
     ap.add_argument("--filter", action="append", default=[], metavar="TYPE:EXPR[:PRIO]")
     ap.add_argument("--stream", default=None, metavar="EXPR")
+    ap.add_argument("--skip-retransmits", action="store_true")
     ap.add_argument("--bidirectional", action="store_true")
     ap.add_argument("--l3-only", action="store_true")
     ap.add_argument("--invert", action="store_true")
@@ -72,6 +77,8 @@ def main():
         raise SystemExit("--chunk / --flow-cap: want a positive count")
     if not a.filter and a.stream is None:
         raise SystemExit("--filter: want at least one (without a filter every packet passes: copy the file)")
+    if a.skip_retransmits and a.stream is None:
+        raise SystemExit("--skip-retransmits: goes with --stream")
     filters = [parse_filter(f) for f in a.filter]
     blob = None
     if a.stream is not None:
@@ -118,6 +125,12 @@ def main():
             bufs += [b for b in (d_blob, d_stab, d_sscr, d_hit, d_stres, d_mres2) if b is not None]
             d_blob.upload(blob)
             d_stab.zero()
+            if a.skip_retransmits:
+                qneed = abi.flow_tcpseq_scratch_bytes(max_n, cap)
+                d_qtab, d_qscr, d_keep = ctx.alloc(128 * cap), ctx.alloc(max(256, qneed)), ctx.alloc(max(16, (max_n + 63) // 64 * 8))
+                d_qres = ctx.alloc(max(64, 64 * len(parts)))
+                bufs += [d_qtab, d_qscr, d_keep, d_qres]
+                d_qtab.zero()
         d_marks.zero()
         ctx.reserve(max_n)
         ctx.flow_track_init(d_state, lay["total"], cap, flags)
@@ -138,7 +151,11 @@ def main():
             ctx.flow_track_update(d_state, batch, d_scratch, need, d_res, flow_id=ids)
             if blob is not None:
                 hit = d_hit.ptr if filters else ver
-                ctx.flow_stream(batch, ids, None, flags, blob, d_blob, d_stab, cap, d_sscr, sneed, d_stres.ptr + 64 * k, hit=hit)
+                keep = None
+                if a.skip_retransmits:   # every packet but the old segments
+                    keep = d_keep
+                    ctx.flow_tcpseq(batch, ids, None, flags, d_qtab, cap, d_qscr, qneed, d_qres.ptr + 64 * k, out_select=d_keep)
+                ctx.flow_stream(batch, ids, keep, flags, blob, d_blob, d_stab, cap, d_sscr, sneed, d_stres.ptr + 64 * k, hit=hit)
                 ctx.flow_mark_update(batch, ids, hit, MARK, d_marks, cap, (d_mres2 if filters else d_mres).ptr + 32 * k)
             if filters:
                 ctx.flow_mark_update(batch, ids, ver, MARK, d_marks, cap, d_mres.ptr + 32 * k)
@@ -168,6 +185,13 @@ def main():
                     out["stream_hit_packets"] += r["hit_packets"]
                     if filters:   # the flows the stream's hits marked first
                         out["marked_flows"] += abi.FlowMarkResult.from_bytes(raw2[32 * k:32 * k + 32]).as_dict()["new_marked_flows"]
+                if a.skip_retransmits:
+                    raw = d_qres.download(np.zeros(64 * len(parts), np.uint8))
+                    out.update(seq_packets=0, old_packets=0)
+                    for k in range(len(parts)):
+                        r = abi.FlowTcpseqResult.from_bytes(raw[64 * k:64 * k + 64]).as_dict()
+                        out["seq_packets"] += r["seq_packets"]
+                        out["old_packets"] += r["old"]
         if a.invert and parts:   # base = the packets that did not pass
             words = d_ver.download(np.zeros(8 * int(word0[-1]), np.uint8)).view(np.uint64)
             d_ver.upload(~words)
