@@ -943,6 +943,81 @@ def decode_flow_tcpseq(rec) -> dict:
     return out
 
 
+# numpy views of bt_flow_reasm_dir (64 B) and bt_flow_reasm_rec (128 B, one per direction): record f belongs to flow number f
+FlowReasmDir = np.dtype({"names": ["d", "next", "have", "stream_packets", "hit_packets", "holes", "dup_packets", "late_packets",
+                                   "dup_bytes", "hole_bytes", "late_bytes"],
+                         "formats": ["<u8", "<i8", "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u8", "<u8", "<u8"],
+                         "offsets": [0, 8, 16, 20, 24, 28, 32, 36, 40, 48, 56], "itemsize": 64})
+FlowReasmRec = np.dtype({"names": ["d"], "formats": [(FlowReasmDir, 2)], "offsets": [0], "itemsize": 128})
+
+
+class FlowReasmOut(ctypes.Structure):
+    """bt_flow_reasm_out (40 B): the optional hit and rest words, and the result."""
+    _fields_ = [("hit", ctypes.c_void_p), ("rest", ctypes.c_void_p), ("result", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2)]
+
+
+class FlowReasmResult(_Counts):
+    """bt_flow_reasm_result (64 B): the counts of a reassembly call."""
+    _fields_ = [("n", ctypes.c_uint32), ("selected", ctypes.c_uint32), ("unkeyed", ctypes.c_uint32), ("bad_ids", ctypes.c_uint32),
+                ("stream_packets", ctypes.c_uint32), ("hit_packets", ctypes.c_uint32), ("new_hit_flows", ctypes.c_uint32),
+                ("holes", ctypes.c_uint32), ("dup_packets", ctypes.c_uint32), ("late_packets", ctypes.c_uint32),
+                ("far_packets", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("stream_bytes", ctypes.c_uint64),
+                ("reserved1", ctypes.c_uint64)]
+
+
+def flow_reasm_scratch_bytes(n: int, flow_cap: int) -> int:
+    """bt_flow_reasm_scratch_bytes (host only)."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_reasm_scratch_bytes(n, flow_cap, ctypes.byref(b)))
+    return b.value
+
+
+def flow_reasm_host(data, desc, flow_id, select, off, table_flags: int, pattern, table: np.ndarray, hit=None, rest=None,
+                    nbytes=None) -> dict:
+    """bt_flow_reasm_host (host only): the TCP segments of the frames desc (packed descriptors) lists
+    in `data` whose bit is set in `select` (verdict-layout u64 words, None = all), whose flow number
+    flow_id[i] is below len(table) and which flow_tcpseq placed (`off`, n int64, its output for the
+    same select) are ordered by sequence position per (flow, direction), trimmed where they overlap,
+    and `pattern` (flow_stream_compile's blob) is matched over the bytes in that order against
+    `table` (FlowReasmRec, in place). hit and rest (ceil(n/64) u64 words each; either may be
+    `select`): the packets from whose delivered bytes a match ends, and the selected packets that
+    were not placed. Returns the result dict."""
+    a = _byte_view(data)
+    keep = a if len(a) else np.zeros(1, np.uint8)
+    d = np.ascontiguousarray(desc, np.uint64)
+    n = len(d)
+    nw = (n + 63) // 64
+    ids = np.ascontiguousarray(flow_id, np.uint32)
+    pat = np.ascontiguousarray(pattern, np.uint8)
+    for arr in (select, hit, rest):
+        if arr is not None and (arr.dtype != np.uint64 or not arr.flags["C_CONTIGUOUS"] or len(arr) < nw):
+            raise ValueError("flow_reasm_host: ceil(n/64) contiguous u64 words for select, hit and rest")
+    if (off is None and n) or (off is not None and (off.dtype != np.int64 or not off.flags["C_CONTIGUOUS"] or len(off) < n)):
+        raise ValueError("flow_reasm_host: n contiguous i8 for off")
+    if len(ids) != n or table.dtype != FlowReasmRec or not table.flags["C_CONTIGUOUS"]:
+        raise ValueError("flow_reasm_host: one flow_id per descriptor and a contiguous FlowReasmRec table")
+    at = lambda x: x.ctypes.data if x is not None and len(x) else None  # noqa: E731
+    res = FlowReasmResult()
+    out = FlowReasmOut(at(hit), at(rest), ctypes.addressof(res), (ctypes.c_uint64 * 2)(0, 0))
+    _check(lib().bt_flow_reasm_host(keep.ctypes.data, len(a) if nbytes is None else nbytes, at(d), n, at(ids), at(select), at(off),
+                                    table_flags, at(pat), len(pat), at(table), len(table), ctypes.byref(out)))
+    return res.as_dict()
+
+
+def decode_flow_reasm(rec) -> dict:
+    """One FlowReasmRec in plain values, per direction: whether the direction was seen, the position
+    up to which its stream was delivered, the matcher's state, and its packets, hits, holes,
+    duplicates and late segments."""
+    r = np.ascontiguousarray(rec, FlowReasmRec).reshape(1)[0]
+    names = ("stream_packets", "hit_packets", "holes", "dup_packets", "late_packets", "dup_bytes", "hole_bytes", "late_bytes")
+    out = {"have": [bool(int(r["d"][k]["have"])) for k in range(2)], "next": [int(r["d"][k]["next"]) for k in range(2)],
+           "state": [int(r["d"][k]["d"]) for k in range(2)]}
+    for name in names:
+        out[name] = [int(r["d"][k][name]) for k in range(2)]
+    out["hit"] = bool(out["hit_packets"][0] or out["hit_packets"][1])
+    return out
+
+
 # bt_flow_track_top_*: the metric a top-K query orders by, and its limit on k
 FLOW_TOP_BYTES, FLOW_TOP_PACKETS, FLOW_TOP_DURATION, FLOW_TOP_TCP_SYN, FLOW_TOP_TCP_RST = range(5)
 FLOW_TOP_MAX_K = 4096
@@ -1174,6 +1249,7 @@ EXPORTS = [
     "bt_flow_stream_compile", "bt_flow_stream_scratch_bytes", "bt_flow_stream_device", "bt_flow_stream_host",
     "bt_time_flow_stream",
     "bt_flow_tcpseq_scratch_bytes", "bt_flow_tcpseq_device", "bt_flow_tcpseq_host", "bt_time_flow_tcpseq",
+    "bt_flow_reasm_scratch_bytes", "bt_flow_reasm_device", "bt_flow_reasm_host", "bt_time_flow_reasm",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -1295,6 +1371,13 @@ def lib() -> ctypes.CDLL:
         "bt_flow_tcpseq_host": (ctypes.c_int, [vp, ctypes.c_uint64, vp, u32, vp, vp, u32, vp, u32, ctypes.POINTER(FlowTcpseqOut)]),
         "bt_time_flow_tcpseq": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
                                                ctypes.POINTER(FlowTcpseqOut), u32, vp, vp]),
+        "bt_flow_reasm_scratch_bytes": (ctypes.c_int, [u32, u32, ctypes.POINTER(ctypes.c_uint64)]),
+        "bt_flow_reasm_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
+                                                ctypes.POINTER(FlowReasmOut), vp]),
+        "bt_flow_reasm_host": (ctypes.c_int, [vp, ctypes.c_uint64, vp, u32, vp, vp, vp, u32, vp, u32, vp, u32,
+                                              ctypes.POINTER(FlowReasmOut)]),
+        "bt_time_flow_reasm": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
+                                              ctypes.POINTER(FlowReasmOut), u32, vp, vp]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -1813,7 +1896,29 @@ class Context:
         _check(lib().bt_flow_tcpseq_device(self.h, ctypes.byref(batch), ptr(flow_id), ptr(select), table_flags, ptr(table), flow_cap,
                                            ptr(scratch), scratch_bytes, ctypes.byref(out), stream))
 
+    def flow_reasm(self, batch: Batch, flow_id, select, off, table_flags: int, pattern, pattern_device, table, flow_cap: int,
+                   scratch, scratch_bytes: int, result, hit=None, rest=None, stream=None):
+        """bt_flow_reasm_device: the TCP segments of the packets of `batch` whose bit is set in `select`
+        (verdict-layout words on the device; None = all; the same words flow_tcpseq took), whose
+        flow number flow_id[i] is below flow_cap and which flow_tcpseq placed (`off`, n int64 on the
+        device) are ordered by sequence position per (flow, direction), trimmed where they overlap,
+        and `pattern` (flow_stream_compile's blob; pattern_device its device copy) is matched over
+        the bytes in that order against `table` (flow_cap FlowReasmRec on the device, zeroed once by
+        the caller). hit and rest (ceil(n/64) u64 words each; either may be `select`) are optional:
+        the packets from whose delivered bytes a match ends, and the selection to hand to
+        flow_stream for everything that was not placed. scratch: flow_reasm_scratch_bytes(n,
+        flow_cap) bytes, 256-byte aligned. result: 64 B (FlowReasmResult), 8-byte aligned. Pointers
+        are addresses or DeviceBuffers. Asynchronous on `stream`: enqueue it behind flow_tcpseq."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        pat = np.ascontiguousarray(pattern, np.uint8)
+        out = FlowReasmOut(ptr(hit), ptr(rest), ptr(result), (ctypes.c_uint64 * 2)(0, 0))
+        _check(lib().bt_flow_reasm_device(self.h, ctypes.byref(batch), ptr(flow_id), ptr(select), ptr(off), table_flags,
+                                          pat.ctypes.data if len(pat) else None, ptr(pattern_device), len(pat), ptr(table), flow_cap,
+                                          ptr(scratch), scratch_bytes, ctypes.byref(out), stream))
+
     # the host-only forms beside their device forms
+    flow_reasm_host = staticmethod(flow_reasm_host)
+    flow_reasm_scratch_bytes = staticmethod(flow_reasm_scratch_bytes)
     flow_tcpseq_host = staticmethod(flow_tcpseq_host)
     flow_tcpseq_scratch_bytes = staticmethod(flow_tcpseq_scratch_bytes)
     flow_stream_host = staticmethod(flow_stream_host)

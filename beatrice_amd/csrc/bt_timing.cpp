@@ -372,6 +372,35 @@ int bt_time_flow_tcpseq(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_
     return BT_OK;
 }
 
+int bt_time_flow_reasm(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select, const int64_t* off,
+                       uint32_t table_flags, const void* pattern, const void* pattern_device, uint32_t pattern_bytes,
+                       bt_flow_reasm_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes, const bt_flow_reasm_out* out,
+                       uint32_t iters, float* ms, float* phase_ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !frames || !frames->n || !iters || !ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, (7u * iters + 1u) / 2u)) return rc;
+    for (uint32_t i = 0; i < iters; ++i) {
+        void* ev[7];
+        for (uint32_t k = 0; k < 7u; ++k) ev[k] = c->timing.tev[7 * i + k];
+        if (int rc = run_flow_reasm(c, frames, flow_id, select, off, table_flags, pattern, pattern_device, pattern_bytes, table, flow_cap,
+                                    scratch, scratch_bytes, out, c->stream, ev)) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) {
+        hipEvent_t* const e = &c->timing.tev[7 * i];
+        HIP_TRY(hipEventElapsedTime(&ms[i], e[0], e[6]));
+        if (!phase_ms) continue;
+        for (uint32_t k = 0; k < 6u; ++k) HIP_TRY(hipEventElapsedTime(&phase_ms[6 * i + k], e[k], e[k + 1]));
+    }
+    return BT_OK;
+}
+
 int bt_time_flow_top(bt_ctx* c, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
                      uint64_t scratch_bytes, const bt_flow_top_out* out, uint32_t iters, float* ms) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return

@@ -96,7 +96,7 @@ extern "C" {
  * bt_flow_mark_select_device, bt_flow_mark_select_host, bt_flow_seq_scratch_bytes,
  * bt_flow_seq_device, bt_flow_seq_host, bt_flow_stream_compile, bt_flow_stream_scratch_bytes,
  * bt_flow_stream_device, bt_flow_stream_host, bt_flow_tcpseq_scratch_bytes, bt_flow_tcpseq_device,
- * bt_flow_tcpseq_host. */
+ * bt_flow_tcpseq_host, bt_flow_reasm_scratch_bytes, bt_flow_reasm_device, bt_flow_reasm_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -1283,6 +1283,90 @@ int  bt_flow_tcpseq_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* 
 int  bt_flow_tcpseq_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_id,
                          const uint64_t* select, uint32_t table_flags, bt_flow_tcpseq_rec* table, uint32_t flow_cap,
                          const bt_flow_tcpseq_out* out);
+
+/* ---- per-flow TCP reassembly: a payload pattern matched in sequence order -------------------
+ * bt_flow_stream_device matches a pattern across packet boundaries in arrival order;
+ * bt_flow_tcpseq_device places every segment in its direction's unwrapped sequence space. This
+ * primitive joins the two: within a call the segments of a (flow, direction) are ordered by
+ * sequence position, what overlaps is trimmed, and the pattern is matched over the bytes in that
+ * order, with the position carried from call to call.
+ * Inputs: those of bt_flow_stream_device, and off: n int64, the `off` output of
+ * bt_flow_tcpseq_device for the same batch, flow_id and `select`. Pass the same `select` as to
+ * that call, not its out_select: a late segment that fills a hole is wanted here. The pattern is
+ * a blob of bt_flow_stream_compile, held to the same predicate.
+ * Packet i participates when its bit is set in `select`, flow_id[i] < flow_cap, off[i] !=
+ * BT_TCPSEQ_OFF_NONE, the walk finds a whole TCP header (the stream matcher's rule with protocol
+ * 6) and its captured payload length plen, by the stream matcher's rule, is > 0. Its data range
+ * is [ds, de) with ds = off[i] + SYN (a SYN's or FIN's sequence number carries no byte) and de =
+ * ds + plen: a snapped segment contributes what was captured, the rest shows as a hole. Sums of
+ * positions wrap as unsigned numbers do and compare as signed ones.
+ * The record of (flow, direction) holds d, the matcher's state after the last delivered byte,
+ * next, the unwrapped position up to which the stream has been delivered, have, and counters.
+ * The reorder window is the call. Per (flow, direction), from the record as the call found it:
+ *   1. base = next with have, else -2^30: a new stream's window is centred on its first-arrived
+ *      segment, whose off is 0.
+ *   2. With have, a segment with de <= next is late: late_packets += 1, late_bytes += plen, and
+ *      it is dropped.
+ *   3. With have, a segment with ds < next < de is trimmed to start at next; dup_bytes += next - ds.
+ *   4. rel = ds' - base. A segment with rel < 0 or rel > 0x7FFE0000 is far: counted in
+ *      *result and dropped. plen < 2^17, so rel + len fits in 31 bits.
+ *   5. The remaining segments are taken in the order (rel, packet index) against a running end
+ *      hi, which starts at 0 with have and at the first segment's rel without.
+ *   6. For each: rel > hi is a hole: holes += 1, hole_bytes += rel - hi, and the matcher's state
+ *      becomes 0 (no match spans missing bytes). rel + len <= hi is a whole duplicate:
+ *      dup_packets += 1, dup_bytes += len, nothing is delivered. Otherwise the bytes [max(rel,
+ *      hi), rel + len) are delivered to the matcher, dup_bytes += max(hi - rel, 0) and
+ *      stream_packets += 1. Then hi = max(hi, rel + len). Where two segments hold different
+ *      bytes for a position, the first in (rel, index) order wins.
+ *   7. After the call next = base + hi, have = 1, d = the state after the last delivered byte. A
+ *      direction none of whose segments got past 2. - 4. keeps next, have and d.
+ *   8. A hole still open at the end of a call is given up: the segment that would have filled it
+ *      is late in the next call. This is what bounds the memory to the record.
+ * out->hit (optional; verdict layout): bit i is set iff a match ends in a byte delivered from
+ * packet i. out->rest (optional): `select` restricted to the packets whose off is
+ * BT_TCPSEQ_OFF_NONE (UDP, and whatever the sequence call did not place): the selection to hand
+ * to bt_flow_stream_device for an arrival-order match of everything else. Each may be `select`,
+ * in place; they may not be one another.
+ * table: flow_cap records bt_flow_reasm_rec (128 B, two bt_flow_reasm_dir), 8-byte aligned,
+ * zeroed once; counts mod 2^32, bytes mod 2^64. It goes through an expire by
+ * bt_flow_track_side_move_device with rec_bytes = 128.
+ * *out->result: selected, unkeyed, bad_ids as in the stream family; stream_packets, stream_bytes
+ * = the packets that delivered a byte and the bytes delivered; hit_packets = the hit bits;
+ * new_hit_flows = the flows with a hit in this call whose record had hit_packets == 0 in both
+ * directions before it; holes, dup_packets, late_packets, far_packets as above.
+ * Asynchronous on `stream`, no allocation, no host synchronisation; n == 0 writes *result in
+ * stream order and nothing else. scratch: bt_flow_reasm_scratch_bytes(n, flow_cap) bytes, 256-byte
+ * aligned. Every output is exact, equal to the host form's and bit-identical from run to run.
+ * BT_E_INVALID_ARGUMENT before the context or any HIP call, as bt_flow_stream_device, with: a null
+ * off (with n > 0); off, rest not 8-byte aligned; hit == rest.
+ * bt_flow_reasm_host: the same on the calling thread as a plain loop, which is the definition. */
+typedef struct bt_flow_reasm_dir {             /* 64 B; all-zero = nothing seen */
+    uint64_t d;                                /* the matcher's state after the last delivered byte */
+    int64_t  next;                             /* the unwrapped position up to which the stream has been delivered */
+    uint32_t have, stream_packets, hit_packets, holes, dup_packets, late_packets;
+    uint64_t dup_bytes, hole_bytes, late_bytes;
+} bt_flow_reasm_dir;
+typedef struct bt_flow_reasm_rec { bt_flow_reasm_dir d[2]; } bt_flow_reasm_rec;   /* 128 B, per direction */
+typedef struct bt_flow_reasm_out {
+    uint64_t* hit; uint64_t* rest;
+    struct bt_flow_reasm_result* result;
+    uint64_t reserved[2];
+} bt_flow_reasm_out;
+typedef struct bt_flow_reasm_result {          /* 64 B, device-visible, 8-byte aligned */
+    uint32_t n, selected, unkeyed, bad_ids, stream_packets, hit_packets, new_hit_flows, holes, dup_packets, late_packets,
+             far_packets, reserved0;
+    uint64_t stream_bytes, reserved1;
+} bt_flow_reasm_result;
+
+int  bt_flow_reasm_scratch_bytes(uint32_t n, uint32_t flow_cap, uint64_t* bytes);     /* host only */
+int  bt_flow_reasm_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id /* device, n */,
+                          const uint64_t* select /* NULL = all n */, const int64_t* off /* device, n */, uint32_t table_flags,
+                          const void* pattern /* host */, const void* pattern_device, uint32_t pattern_bytes,
+                          bt_flow_reasm_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes,
+                          const bt_flow_reasm_out* out, void* stream);
+int  bt_flow_reasm_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_id,
+                        const uint64_t* select, const int64_t* off, uint32_t table_flags, const void* pattern,
+                        uint32_t pattern_bytes, bt_flow_reasm_rec* table, uint32_t flow_cap, const bt_flow_reasm_out* out);
 
 /* ---- top-K flows of a tracker: the largest flows by a measure, selected on the device ------
  * bt_flow_track_top_device: the k largest flows of the tracker at `state` by opts->metric,

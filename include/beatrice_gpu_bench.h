@@ -167,6 +167,16 @@ int  bt_time_flow_stream(bt_ctx* ctx, const bt_batch* frames, const uint32_t* fl
 int  bt_time_flow_tcpseq(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select,
                          uint32_t table_flags, bt_flow_tcpseq_rec* table, uint32_t flow_cap, void* scratch,
                          uint64_t scratch_bytes, const bt_flow_tcpseq_out* out, uint32_t iters, float* ms, float* phase_ms);
+/* bt_flow_reasm_device `iters` times on the context's stream into the same table (from the second
+ * call on every segment lies below `next`: late) and the same scratch; ms[i] = call i's kernels, from
+ * the first one's start to the last one's end, events recorded by the kernels' own dispatches (the
+ * two memsets in front are outside). phase_ms (optional, 6 * iters): call i's classification +
+ * compaction, first sort (4 passes, by position), rekey + second sort (by flow and direction), carry
+ * scan + join + emit, match, and commit, in that order. */
+int  bt_time_flow_reasm(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select, const int64_t* off,
+                        uint32_t table_flags, const void* pattern, const void* pattern_device, uint32_t pattern_bytes,
+                        bt_flow_reasm_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes,
+                        const bt_flow_reasm_out* out, uint32_t iters, float* ms, float* phase_ms);
 /* What the tracker replaces, `iters` times: copy_ms[i] = the n_flows records of a per-batch table
  * (flows, on the device) copied to pinned host memory (wall clock, the wait included), merge_ms[i]
  * = those records merged into the host tracker state at host_state (bt_flow_track_init_host's) on

@@ -5,7 +5,7 @@ the file (the NetFlow / conntrack view of a capture).
 Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [--bidirectional] [--l3-only]
                                   [--top N] [--format csv|json] [--chunk-packets N]
                                   [--track [--idle SECONDS] [--flow-cap N] [--tcp [--closed-idle SECONDS]]
-                                           [--stats] [--seq] [--by bytes|packets|duration|syn|rst]
+                                           [--stats] [--seq] [--reasm EXPR] [--by bytes|packets|duration|syn|rst]
                                            [--hosts [--top N --by bytes|packets|flows]]]
   --filter         as tools/pcap_filter.py takes it; only passing packets are counted
   --bidirectional  both directions of a conversation are one flow (BT_FLOWTAB_BIDIRECTIONAL): the
@@ -45,6 +45,15 @@ Usage: python tools/pcap_flows.py --in a.pcap [--filter TYPE:EXPR[:PRIO] ...] [-
                    gap_packets 0 certain duplicates), gap_packets (ahead of everything seen: a loss or reordering in
                    front), overlap_packets, old_bytes and gap_bytes. With --idle the record of a flow that ages out
                    leaves with it. Not with --top or --hosts.
+  --reasm EXPR     with --track: a TCP reassembly side table beside the tracker (bt_flow_tcpseq_device, then
+                   bt_flow_reasm_device behind every update): EXPR (a bounded-memory pattern, as tools/pcap_sessions.py
+                   --stream takes it) is matched over each direction's bytes in sequence order, the segments of a chunk
+                   reordered, overlaps trimmed, no match across a hole; a hole still open at a chunk's end is given up.
+                   Adds per direction (the second with the suffix _rev) reasm_packets (segments that delivered a byte),
+                   reasm_hits (packets in which a match ends), holes, hole_bytes, dup_packets, dup_bytes, late_packets,
+                   late_bytes and delivered_to (the position up to which the stream was delivered, counted from the
+                   direction's first-arrived segment; empty for a direction without data). With --idle the record of a
+                   flow that ages out leaves with it. Not with --top or --hosts.
   --by MEASURE     with --track and --top N, N <= 4096: what the top is ordered by, largest first and the
                    earliest-seen flow first among equals: bytes (default), packets (both directions), duration
                    (last minus first packet time by the pcap record headers), syn or rst (with --tcp: packets with
@@ -91,6 +100,9 @@ STAT_COLUMNS = ("protocols", "proto_max") + STAT_DIR_COLUMNS + tuple(c + "_rev" 
 RTT_COLUMNS = ("initiator", "rtt_server", "rtt_client")
 SEQ_DIR_COLUMNS = ("seq_packets", "old_packets", "gap_packets", "overlap_packets", "old_bytes", "gap_bytes")
 SEQ_COLUMNS = SEQ_DIR_COLUMNS + tuple(c + "_rev" for c in SEQ_DIR_COLUMNS)
+REASM_DIR_COLUMNS = ("reasm_packets", "reasm_hits", "holes", "hole_bytes", "dup_packets", "dup_bytes", "late_packets", "late_bytes",
+                     "delivered_to")
+REASM_COLUMNS = REASM_DIR_COLUMNS + tuple(c + "_rev" for c in REASM_DIR_COLUMNS)
 U64_MAX = (1 << 64) - 1
 HOST_COLUMNS = ("address", "flows_src", "flows_dst", "packets_sent", "bytes_sent", "packets_received", "bytes_received",
                 "first_seen", "last_seen")
@@ -155,6 +167,16 @@ def describe_seq(r: dict, rec):
             r[c + suffix] = d[c][k]
 
 
+def describe_reasm(r: dict, rec):
+    """The --reasm columns of one output line from a bt_flow_reasm_rec."""
+    d = abi.decode_flow_reasm(rec)
+    names = {"reasm_packets": "stream_packets", "reasm_hits": "hit_packets"}
+    for k, suffix in enumerate(("", "_rev")):
+        for c in REASM_DIR_COLUMNS[:-1]:
+            r[c + suffix] = d[names.get(c, c)][k]
+        r["delivered_to" + suffix] = d["next"][k] if d["have"][k] else None
+
+
 def merge(table: dict, flows: np.ndarray, lo: int):
     """Add one chunk's records (packet numbers relative to `lo`) to the file's table."""
     for f in flows:
@@ -188,7 +210,7 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         ts = word(0) * np.uint64(unit) + word(4)
     rows = []
 
-    def lines(recs, side=None, stat=None, seq=None):
+    def lines(recs, side=None, stat=None, seq=None, reasm=None):
         for k, f in enumerate(recs):
             v = [int(f["packets"][0]), int(f["packets"][1]), int(f["bytes"][0]), int(f["bytes"][1]),
                  int(starts[f["first_batch"]]) + int(f["first"]), int(starts[f["last_batch"]]) + int(f["last"])]
@@ -206,6 +228,8 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
                 describe_stats(r, stat[k], v[0:2], v[2:4], bool(flags & abi.FLOWTAB_BIDIRECTIONAL))
             if seq is not None:
                 describe_seq(r, seq[k])
+            if reasm is not None:
+                describe_reasm(r, reasm[k])
             rows.append(r)
 
     if a.tcp and timed:
@@ -217,7 +241,8 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
     if timed:
         d_ts, d_xscratch, d_xres, d_exp = ctx.alloc(max(16, max_n * 8)), ctx.alloc(xneed), ctx.alloc(32), ctx.alloc(104 * cap)
         bufs += [d_ts, d_xscratch, d_xres, d_exp]
-    sided = a.stats or a.seq   # side tables that follow an expire's remap
+    seqd = a.seq or a.reasm is not None   # the reassembly takes its offsets from the sequence spaces
+    sided = a.stats or seqd   # side tables that follow an expire's remap
     if a.tcp or sided:   # the update's flow ids feed the side tables
         d_ids = ctx.alloc(max(16, max_n * 4))
         bufs.append(d_ids)
@@ -232,7 +257,7 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         if timed:
             d_exp_stat = ctx.alloc(128 * cap)
             bufs.append(d_exp_stat)
-    if a.seq:   # the sequence spaces, zeroed once; with --idle they follow the expire's remap
+    if seqd:   # the sequence spaces, zeroed once; with --idle they follow the expire's remap
         qneed = abi.flow_tcpseq_scratch_bytes(max_n, cap)
         d_seq, d_qscratch, d_qres = ctx.alloc(128 * cap), ctx.alloc(max(256, qneed)), ctx.alloc(64)
         d_seq.zero()
@@ -240,6 +265,16 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         if timed:
             d_exp_seq = ctx.alloc(128 * cap)
             bufs.append(d_exp_seq)
+    if a.reasm is not None:   # the reassembly records, zeroed once; with --idle they follow the expire's remap
+        rneed = abi.flow_reasm_scratch_bytes(max_n, cap)
+        d_reasm, d_rscratch, d_rres = ctx.alloc(128 * cap), ctx.alloc(max(256, rneed)), ctx.alloc(64)
+        d_off, d_blob = ctx.alloc(max(16, 8 * max_n)), ctx.alloc(len(a.blob))
+        d_reasm.zero()
+        d_blob.upload(a.blob)
+        bufs += [d_reasm, d_rscratch, d_rres, d_off, d_blob]
+        if timed:
+            d_exp_reasm = ctx.alloc(128 * cap)
+            bufs.append(d_exp_reasm)
     if a.tcp:   # the side table, zeroed once
         d_tcp, d_tres = ctx.alloc(16 * cap), ctx.alloc(32)
         d_tcp.zero()
@@ -277,8 +312,10 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
             ctx.flow_tcp_update(batch, d_ids, flags, d_tcp, cap, d_tres)
         if a.stats:
             ctx.flow_stat_update(batch, d_ids, flags, d_stat, cap, d_sres, ts=d_ts)
-        if a.seq:   # unselected packets carry the UNSELECTED sentinel: they are in no sequence space
-            ctx.flow_tcpseq(batch, d_ids, None, flags, d_seq, cap, d_qscratch, qneed, d_qres)
+        if seqd:   # unselected packets carry the UNSELECTED sentinel: they are in no sequence space
+            ctx.flow_tcpseq(batch, d_ids, None, flags, d_seq, cap, d_qscratch, qneed, d_qres, off=d_off if a.reasm is not None else None)
+        if a.reasm is not None:   # the chunk's segments in sequence order, behind their offsets
+            ctx.flow_reasm(batch, d_ids, None, d_off, flags, a.blob, d_blob, d_reasm, cap, d_rscratch, rneed, d_rres)
         if timed:   # what aged out is printed now: its count and records come back, nothing else
             if a.tcp:
                 ctx.flow_track_expire_tcp(d_state, int(ts[hi - 1]), int(a.idle * unit), closed, d_tcp, d_xscratch, xneed, d_xres,
@@ -288,15 +325,18 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
                                       remap=d_remap if sided else None)
             if a.stats:   # the statistics of the flows that stay move up, those of the flows that leave come out
                 ctx.flow_track_side_move(d_stat, 128, cap, d_remap, d_xres, d_mscratch, mneed, expired_side=d_exp_stat, expired_cap=cap)
-            if a.seq:   # and so do the sequence spaces
+            if seqd:   # and so do the sequence spaces
                 ctx.flow_track_side_move(d_seq, 128, cap, d_remap, d_xres, d_mscratch, mneed, expired_side=d_exp_seq, expired_cap=cap)
+            if a.reasm is not None:   # and the reassembly records
+                ctx.flow_track_side_move(d_reasm, 128, cap, d_remap, d_xres, d_mscratch, mneed, expired_side=d_exp_reasm, expired_cap=cap)
             ctx.synchronize()
             x = abi.FlowTrackExpireResult.from_bytes(d_xres.download(np.zeros(32, np.uint8))).as_dict()
             if x["n_expired"]:
                 lines(d_exp.download(np.zeros(104 * x["n_expired"], np.uint8)).view(abi.FlowTrackRec),
                       d_exp_tcp.download(np.zeros(16 * x["n_expired"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None,
                       d_exp_stat.download(np.zeros(128 * x["n_expired"], np.uint8)).view(abi.FlowStatRec) if a.stats else None,
-                      d_exp_seq.download(np.zeros(128 * x["n_expired"], np.uint8)).view(abi.FlowTcpseqRec) if a.seq else None)
+                      d_exp_seq.download(np.zeros(128 * x["n_expired"], np.uint8)).view(abi.FlowTcpseqRec) if a.seq else None,
+                      d_exp_reasm.download(np.zeros(128 * x["n_expired"], np.uint8)).view(abi.FlowReasmRec) if a.reasm is not None else None)
     if on_device:   # behind the last update and side table update, on their stream
         ctx.flow_track_top(d_state, TOP_BY[a.by], a.top, d_tscratch, tneed, d_top_res, top=d_top, tcp=d_tcp if a.tcp else None,
                            top_tcp=d_top_tcp if a.tcp else None)
@@ -329,7 +369,8 @@ def track(a, ctx, filters, flags, data, info, off, ln, parts, totals) -> list:
         lines(both[lay["records"]:].view(abi.FlowTrackRec),
               d_tcp.download(np.zeros(16 * hdr["n_flows"], np.uint8)).view(abi.FlowTcpRec) if a.tcp else None,
               d_stat.download(np.zeros(128 * hdr["n_flows"], np.uint8)).view(abi.FlowStatRec) if a.stats else None,
-              d_seq.download(np.zeros(128 * hdr["n_flows"], np.uint8)).view(abi.FlowTcpseqRec) if a.seq else None)
+              d_seq.download(np.zeros(128 * hdr["n_flows"], np.uint8)).view(abi.FlowTcpseqRec) if a.seq else None,
+              d_reasm.download(np.zeros(128 * hdr["n_flows"], np.uint8)).view(abi.FlowReasmRec) if a.reasm is not None else None)
     totals["selected"], totals["no_key"] = hdr["selected_packets"], hdr["none_packets"]
     abi.Context.flow_track_forget(d_state)   # before its memory goes back
     for b in bufs:
@@ -385,6 +426,7 @@ def main():
     ap.add_argument("--hosts", action="store_true")
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--seq", action="store_true")
+    ap.add_argument("--reasm", default=None, metavar="EXPR")
     a = ap.parse_args()
     if a.chunk_packets < 0 or a.top < 0:
         raise SystemExit("--chunk-packets / --top: want a positive count")
@@ -402,6 +444,13 @@ def main():
         raise SystemExit("--stats: only with --track, and without --top and --hosts")
     if a.seq and (not a.track or a.top or a.hosts):
         raise SystemExit("--seq: only with --track, and without --top and --hosts")
+    if a.reasm is not None and (not a.track or a.top or a.hosts):
+        raise SystemExit("--reasm: only with --track, and without --top and --hosts")
+    if a.reasm is not None:
+        try:
+            a.blob, _ = abi.flow_stream_compile(a.reasm)
+        except abi.BtError as e:
+            raise SystemExit(f"pcap_flows: --reasm: {e}")
     if a.hosts and (not a.track or a.idle is not None):
         raise SystemExit("--hosts: only with --track, and without --idle")
     if a.hosts and a.by is not None and (a.by not in HOSTS_BY or not a.top):
@@ -446,6 +495,8 @@ def main():
         columns += STAT_COLUMNS + (RTT_COLUMNS if a.bidirectional else ())
     if a.seq:
         columns += SEQ_COLUMNS
+    if a.reasm is not None:
+        columns += REASM_COLUMNS
     if a.hosts:   # host records in order of first appearance; a top is sorted here (stable: ties stay in that order)
         columns = HOST_COLUMNS + (HOST_TCP_COLUMNS if a.tcp else ())
         if a.top:

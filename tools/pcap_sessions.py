@@ -2,7 +2,7 @@
 --invert, drop those connections whole): the session view of tools/pcap_filter.py, decided on the GPU.
 
 Usage: python tools/pcap_sessions.py --in a.pcap --out b.pcap --filter TYPE:EXPR[:PRIO] ...
-                                     [--stream EXPR [--skip-retransmits]] [--bidirectional] [--l3-only] [--invert]
+                                     [--stream EXPR [--skip-retransmits | --reassemble]] [--bidirectional] [--l3-only] [--invert]
                                      [--flow-cap N] [--chunk PACKETS]
   --filter         as tools/pcap_filter.py takes it
   --stream EXPR    also (or, without --filter, only) select the connections in whose payload stream EXPR matches,
@@ -12,6 +12,11 @@ Usage: python tools/pcap_sessions.py --in a.pcap --out b.pcap --filter TYPE:EXPR
   --skip-retransmits  with --stream: classify the TCP segments first (bt_flow_tcpseq_device) and keep those whose bytes
                    all lie at or below the highest sequence number seen (retransmitted or late) out of the stream, so
                    that HE, LL, LL again, O reads HELLO and not HELLLLO
+  --reassemble     with --stream: match TCP in sequence order. bt_flow_tcpseq_device places every segment,
+                   bt_flow_reasm_device orders each chunk's segments by position, trims what overlaps and cuts the
+                   matcher at a hole, so LO before HEL still reads HELLO and a late segment that fills a hole is used;
+                   everything it does not place (UDP) goes through bt_flow_stream_device in arrival order. The reorder
+                   window is the chunk. It supersedes --skip-retransmits: giving both is an error
   --bidirectional  both directions of a conversation are one session (BT_FLOWTAB_BIDIRECTIONAL)
   --l3-only        never key on ports (BT_FLOWTAB_L3_ONLY): a session is a pair of addresses
   --invert         write the complement: every packet that is in no session with a passing packet
@@ -36,7 +41,10 @@ With --stream, pass one per chunk is: the filter (if any), the tracker update, b
 against one stream table for the whole file, bt_flow_mark_update_device with the stream's hits (and, with a filter, a
 second one with the verdict), then pass two as above; without a filter the stream's hit words stand where the verdict's do.
 Prints one JSON line: packets, hit_packets, flows, marked_flows, unkeyed_hits, written_packets, written_bytes, and with
---stream also stream_packets, stream_bytes, stream_hit_packets, and with --skip-retransmits seq_packets and old_packets.
+--stream also stream_packets, stream_bytes, stream_hit_packets, and with --skip-retransmits seq_packets and old_packets;
+with --reassemble seq_packets, old_packets, reasm_packets, reasm_bytes, reasm_hit_packets, holes, dup_packets, late_packets
+and far_packets. hit_packets stays what it is without the option: the verdict's hit packets, or without a filter the
+arrival-order matcher's; the reassembly's are reasm_hit_packets, and marked_flows counts a flow whichever call marked it first.
 """
 from __future__ import annotations
 
@@ -66,6 +74,7 @@ def main():
     ap.add_argument("--filter", action="append", default=[], metavar="TYPE:EXPR[:PRIO]")
     ap.add_argument("--stream", default=None, metavar="EXPR")
     ap.add_argument("--skip-retransmits", action="store_true")
+    ap.add_argument("--reassemble", action="store_true")
     ap.add_argument("--bidirectional", action="store_true")
     ap.add_argument("--l3-only", action="store_true")
     ap.add_argument("--invert", action="store_true")
@@ -79,6 +88,10 @@ def main():
         raise SystemExit("--filter: want at least one (without a filter every packet passes: copy the file)")
     if a.skip_retransmits and a.stream is None:
         raise SystemExit("--skip-retransmits: goes with --stream")
+    if a.reassemble and a.stream is None:
+        raise SystemExit("--reassemble: goes with --stream")
+    if a.reassemble and a.skip_retransmits:
+        raise SystemExit("--reassemble: supersedes --skip-retransmits, give one of them")
     filters = [parse_filter(f) for f in a.filter]
     blob = None
     if a.stream is not None:
@@ -125,12 +138,19 @@ def main():
             bufs += [b for b in (d_blob, d_stab, d_sscr, d_hit, d_stres, d_mres2) if b is not None]
             d_blob.upload(blob)
             d_stab.zero()
-            if a.skip_retransmits:
+            if a.skip_retransmits or a.reassemble:
                 qneed = abi.flow_tcpseq_scratch_bytes(max_n, cap)
                 d_qtab, d_qscr, d_keep = ctx.alloc(128 * cap), ctx.alloc(max(256, qneed)), ctx.alloc(max(16, (max_n + 63) // 64 * 8))
                 d_qres = ctx.alloc(max(64, 64 * len(parts)))
                 bufs += [d_qtab, d_qscr, d_keep, d_qres]
                 d_qtab.zero()
+            if a.reassemble:
+                rneed = abi.flow_reasm_scratch_bytes(max_n, cap)
+                d_off, d_rtab, d_rscr = ctx.alloc(max(16, 8 * max_n)), ctx.alloc(128 * cap), ctx.alloc(max(256, rneed))
+                d_rhit = ctx.alloc(max(16, (max_n + 63) // 64 * 8))
+                d_rres, d_mres3 = ctx.alloc(max(64, 64 * len(parts))), ctx.alloc(max(32, 32 * len(parts)))
+                bufs += [d_off, d_rtab, d_rscr, d_rhit, d_rres, d_mres3]
+                d_rtab.zero()
         d_marks.zero()
         ctx.reserve(max_n)
         ctx.flow_track_init(d_state, lay["total"], cap, flags)
@@ -155,6 +175,12 @@ def main():
                 if a.skip_retransmits:   # every packet but the old segments
                     keep = d_keep
                     ctx.flow_tcpseq(batch, ids, None, flags, d_qtab, cap, d_qscr, qneed, d_qres.ptr + 64 * k, out_select=d_keep)
+                if a.reassemble:   # TCP in sequence order; what was not placed stays for the arrival-order matcher
+                    keep = d_keep
+                    ctx.flow_tcpseq(batch, ids, None, flags, d_qtab, cap, d_qscr, qneed, d_qres.ptr + 64 * k, off=d_off)
+                    ctx.flow_reasm(batch, ids, None, d_off, flags, blob, d_blob, d_rtab, cap, d_rscr, rneed, d_rres.ptr + 64 * k,
+                                   hit=d_rhit, rest=d_keep)
+                    ctx.flow_mark_update(batch, ids, d_rhit, MARK, d_marks, cap, d_mres3.ptr + 32 * k)
                 ctx.flow_stream(batch, ids, keep, flags, blob, d_blob, d_stab, cap, d_sscr, sneed, d_stres.ptr + 64 * k, hit=hit)
                 ctx.flow_mark_update(batch, ids, hit, MARK, d_marks, cap, (d_mres2 if filters else d_mres).ptr + 32 * k)
             if filters:
@@ -185,13 +211,28 @@ def main():
                     out["stream_hit_packets"] += r["hit_packets"]
                     if filters:   # the flows the stream's hits marked first
                         out["marked_flows"] += abi.FlowMarkResult.from_bytes(raw2[32 * k:32 * k + 32]).as_dict()["new_marked_flows"]
-                if a.skip_retransmits:
+                if a.skip_retransmits or a.reassemble:
                     raw = d_qres.download(np.zeros(64 * len(parts), np.uint8))
                     out.update(seq_packets=0, old_packets=0)
                     for k in range(len(parts)):
                         r = abi.FlowTcpseqResult.from_bytes(raw[64 * k:64 * k + 64]).as_dict()
                         out["seq_packets"] += r["seq_packets"]
                         out["old_packets"] += r["old"]
+                if a.reassemble:
+                    raw, raw3 = d_rres.download(np.zeros(64 * len(parts), np.uint8)), d_mres3.download(np.zeros(32 * len(parts), np.uint8))
+                    names = ("holes", "dup_packets", "late_packets", "far_packets")
+                    out.update(reasm_packets=0, reasm_bytes=0, reasm_hit_packets=0, **{name: 0 for name in names})
+                    for k in range(len(parts)):
+                        r = abi.FlowReasmResult.from_bytes(raw[64 * k:64 * k + 64]).as_dict()
+                        if r["bad_ids"]:
+                            raise SystemExit("pcap_sessions: the tracker's flow ids do not fit the reassembly table")
+                        out["reasm_packets"] += r["stream_packets"]
+                        out["reasm_bytes"] += r["stream_bytes"]
+                        out["reasm_hit_packets"] += r["hit_packets"]
+                        for name in names:
+                            out[name] += r[name]
+                        # the flows the reassembly's hits marked first; its hit packets are reasm_hit_packets, as the stream's are stream_hit_packets
+                        out["marked_flows"] += abi.FlowMarkResult.from_bytes(raw3[32 * k:32 * k + 32]).as_dict()["new_marked_flows"]
         if a.invert and parts:   # base = the packets that did not pass
             words = d_ver.download(np.zeros(8 * int(word0[-1]), np.uint8)).view(np.uint64)
             d_ver.upload(~words)
