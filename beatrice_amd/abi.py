@@ -1018,6 +1018,70 @@ def decode_flow_reasm(rec) -> dict:
     return out
 
 
+# bt_flow_follow_*: the flag bits of a run, and bt_flow_follow_run (32 B) as a numpy view
+FOLLOW_DIR, FOLLOW_NEW, FOLLOW_HOLE = 1, 2, 4
+FlowFollowRun = np.dtype({"names": ["flow", "flags", "at", "pos", "len"], "formats": ["<u4", "<u4", "<u8", "<i8", "<u8"],
+                          "offsets": [0, 4, 8, 16, 24], "itemsize": 32})
+
+
+class FlowFollowOut(ctypes.Structure):
+    """bt_flow_follow_out (64 B): the bytes and their capacity, the runs and theirs, the optional place array, the result."""
+    _fields_ = [("bytes", ctypes.c_void_p), ("cap", ctypes.c_uint64), ("runs", ctypes.c_void_p), ("run_cap", ctypes.c_uint32),
+                ("reserved0", ctypes.c_uint32), ("place", ctypes.c_void_p), ("result", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2)]
+
+
+class FlowFollowResult(_Counts):
+    """bt_flow_follow_result (32 B): the bytes and runs of a follow call, and how many of each were written."""
+    _fields_ = [("total", ctypes.c_uint64), ("written", ctypes.c_uint64), ("n_runs", ctypes.c_uint32), ("runs_written", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint64)]
+
+
+def flow_follow_scratch_bytes(n: int, flow_cap: int) -> int:
+    """bt_flow_follow_scratch_bytes (host only)."""
+    b = ctypes.c_uint64(0)
+    _check(lib().bt_flow_follow_scratch_bytes(n, flow_cap, ctypes.byref(b)))
+    return b.value
+
+
+def flow_follow_host(data, desc, flow_id, select, off, table_flags: int, pattern, table: np.ndarray, out_bytes=None, runs=None,
+                     place=None, hit=None, rest=None, nbytes=None) -> tuple:
+    """bt_flow_follow_host (host only): flow_reasm_host's work on `table` (FlowReasmRec, in place), with
+    every delivered byte written to out_bytes (a contiguous u8 array, its length the capacity; None:
+    a size query), the runs between holes to runs (a contiguous FlowFollowRun array, its length the
+    capacity; None: none) and each packet's output offset to place (n u64; optional). pattern: a
+    flow_stream_compile blob, or None for the plain follow (nothing matched, hit zero). Returns (the
+    reassembly's result dict, the follow's result dict)."""
+    a = _byte_view(data)
+    keep = a if len(a) else np.zeros(1, np.uint8)
+    d = np.ascontiguousarray(desc, np.uint64)
+    n = len(d)
+    nw = (n + 63) // 64
+    ids = np.ascontiguousarray(flow_id, np.uint32)
+    pat = None if pattern is None else np.ascontiguousarray(pattern, np.uint8)
+    for arr in (select, hit, rest):
+        if arr is not None and (arr.dtype != np.uint64 or not arr.flags["C_CONTIGUOUS"] or len(arr) < nw):
+            raise ValueError("flow_follow_host: ceil(n/64) contiguous u64 words for select, hit and rest")
+    if (off is None and n) or (off is not None and (off.dtype != np.int64 or not off.flags["C_CONTIGUOUS"] or len(off) < n)):
+        raise ValueError("flow_follow_host: n contiguous i8 for off")
+    if len(ids) != n or table.dtype != FlowReasmRec or not table.flags["C_CONTIGUOUS"]:
+        raise ValueError("flow_follow_host: one flow_id per descriptor and a contiguous FlowReasmRec table")
+    if out_bytes is not None and (out_bytes.dtype != np.uint8 or not out_bytes.flags["C_CONTIGUOUS"]):
+        raise ValueError("flow_follow_host: a contiguous u8 array for out_bytes")
+    if runs is not None and (runs.dtype != FlowFollowRun or not runs.flags["C_CONTIGUOUS"]):
+        raise ValueError("flow_follow_host: a contiguous FlowFollowRun array for runs")
+    if place is not None and (place.dtype != np.uint64 or not place.flags["C_CONTIGUOUS"] or len(place) < n):
+        raise ValueError("flow_follow_host: n contiguous u64 for place")
+    at = lambda x: x.ctypes.data if x is not None and len(x) else None  # noqa: E731
+    res, fres = FlowReasmResult(), FlowFollowResult()
+    out = FlowReasmOut(at(hit), at(rest), ctypes.addressof(res), (ctypes.c_uint64 * 2)(0, 0))
+    fo = FlowFollowOut(at(out_bytes), 0 if out_bytes is None else len(out_bytes), at(runs), 0 if runs is None else len(runs), 0,
+                       at(place), ctypes.addressof(fres), (ctypes.c_uint64 * 2)(0, 0))
+    _check(lib().bt_flow_follow_host(keep.ctypes.data, len(a) if nbytes is None else nbytes, at(d), n, at(ids), at(select), at(off),
+                                     table_flags, at(pat), 0 if pat is None else len(pat), at(table), len(table), ctypes.byref(out),
+                                     ctypes.byref(fo)))
+    return res.as_dict(), fres.as_dict()
+
+
 # bt_flow_track_top_*: the metric a top-K query orders by, and its limit on k
 FLOW_TOP_BYTES, FLOW_TOP_PACKETS, FLOW_TOP_DURATION, FLOW_TOP_TCP_SYN, FLOW_TOP_TCP_RST = range(5)
 FLOW_TOP_MAX_K = 4096
@@ -1250,6 +1314,7 @@ EXPORTS = [
     "bt_time_flow_stream",
     "bt_flow_tcpseq_scratch_bytes", "bt_flow_tcpseq_device", "bt_flow_tcpseq_host", "bt_time_flow_tcpseq",
     "bt_flow_reasm_scratch_bytes", "bt_flow_reasm_device", "bt_flow_reasm_host", "bt_time_flow_reasm",
+    "bt_flow_follow_scratch_bytes", "bt_flow_follow_device", "bt_flow_follow_host", "bt_time_flow_follow",
 ]
 
 DEST_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)   # bt_format_records_to's dest
@@ -1378,6 +1443,13 @@ def lib() -> ctypes.CDLL:
                                               ctypes.POINTER(FlowReasmOut)]),
         "bt_time_flow_reasm": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
                                               ctypes.POINTER(FlowReasmOut), u32, vp, vp]),
+        "bt_flow_follow_scratch_bytes": (ctypes.c_int, [u32, u32, ctypes.POINTER(ctypes.c_uint64)]),
+        "bt_flow_follow_device": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
+                                                 ctypes.POINTER(FlowReasmOut), ctypes.POINTER(FlowFollowOut), vp]),
+        "bt_flow_follow_host": (ctypes.c_int, [vp, ctypes.c_uint64, vp, u32, vp, vp, vp, u32, vp, u32, vp, u32,
+                                               ctypes.POINTER(FlowReasmOut), ctypes.POINTER(FlowFollowOut)]),
+        "bt_time_flow_follow": (ctypes.c_int, [vp, ctypes.POINTER(Batch), vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, ctypes.c_uint64,
+                                               ctypes.POINTER(FlowReasmOut), ctypes.POINTER(FlowFollowOut), u32, vp, vp]),
         "bt_pcap_index": (ctypes.c_int, [vp, u64, ctypes.POINTER(PcapInfo), vp, u64, ctypes.POINTER(u64)]),
         "bt_pcap_filter": (ctypes.c_int, [vp, vp, u64, vp, u64, ctypes.POINTER(PcapResult)]),
         "bt_parse_filter_device_async": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Outputs), vp,
@@ -1916,7 +1988,30 @@ class Context:
                                           pat.ctypes.data if len(pat) else None, ptr(pattern_device), len(pat), ptr(table), flow_cap,
                                           ptr(scratch), scratch_bytes, ctypes.byref(out), stream))
 
+    def flow_follow(self, batch: Batch, flow_id, select, off, table_flags: int, pattern, pattern_device, table, flow_cap: int,
+                    scratch, scratch_bytes: int, result, follow_result, out_bytes=None, cap: int = 0, runs=None, run_cap: int = 0,
+                    place=None, hit=None, rest=None, stream=None):
+        """bt_flow_follow_device: flow_reasm's work on the same arguments and the same `table`, with every
+        delivered byte of the call written to out_bytes (cap bytes on the device; None with cap 0: a
+        size query) in ascending (flow, direction) and sequence order, the runs between holes to runs
+        (run_cap FlowFollowRun on the device) and each packet's output offset to place (n u64 on the
+        device; optional). pattern None (then pattern_device None as well): the plain follow, nothing
+        is matched and hit is written as zeros. scratch: flow_follow_scratch_bytes(n, flow_cap)
+        bytes, 256-byte aligned. result: 64 B (FlowReasmResult); follow_result: 32 B
+        (FlowFollowResult); both 8-byte aligned. Pointers are addresses or DeviceBuffers.
+        Asynchronous on `stream`: enqueue it behind flow_tcpseq."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.uint8)
+        out = FlowReasmOut(ptr(hit), ptr(rest), ptr(result), (ctypes.c_uint64 * 2)(0, 0))
+        fo = FlowFollowOut(ptr(out_bytes), cap, ptr(runs), run_cap, 0, ptr(place), ptr(follow_result), (ctypes.c_uint64 * 2)(0, 0))
+        _check(lib().bt_flow_follow_device(self.h, ctypes.byref(batch), ptr(flow_id), ptr(select), ptr(off), table_flags,
+                                           pat.ctypes.data if pat is not None and len(pat) else None, ptr(pattern_device),
+                                           0 if pat is None else len(pat), ptr(table), flow_cap, ptr(scratch), scratch_bytes,
+                                           ctypes.byref(out), ctypes.byref(fo), stream))
+
     # the host-only forms beside their device forms
+    flow_follow_host = staticmethod(flow_follow_host)
+    flow_follow_scratch_bytes = staticmethod(flow_follow_scratch_bytes)
     flow_reasm_host = staticmethod(flow_reasm_host)
     flow_reasm_scratch_bytes = staticmethod(flow_reasm_scratch_bytes)
     flow_tcpseq_host = staticmethod(flow_tcpseq_host)

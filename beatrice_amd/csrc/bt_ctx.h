@@ -300,6 +300,12 @@ int run_flow_reasm(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, c
                    bt_flow_reasm_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes, const bt_flow_reasm_out* out,
                    hipStream_t st, void* const* ev);
 
+// bt_flowfollow_host.cpp (bt_timing.cpp's bt_time_flow_follow times the same launches; ev: nullptr or nine events)
+int run_flow_follow(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select, const int64_t* off,
+                    uint32_t table_flags, const void* pattern, const void* pattern_device, uint32_t pattern_bytes,
+                    bt_flow_reasm_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes, const bt_flow_reasm_out* out,
+                    const bt_flow_follow_out* fo, hipStream_t st, void* const* ev);
+
 // bt_flowtop_host.cpp (bt_timing.cpp's bt_time_flow_top times the same launches)
 int run_flow_track_top(bt_ctx* c, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
                        uint64_t scratch_bytes, const bt_flow_top_out* out, hipStream_t st, hipEvent_t e0, hipEvent_t e1);

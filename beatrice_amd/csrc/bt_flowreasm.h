@@ -146,18 +146,18 @@ inline bool flowreasm_common_args(const uint32_t* flow_id, uint32_t n, const uin
 inline int flowreasm_args(const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select, const int64_t* off,
                           uint32_t table_flags, const void* pattern, const void* pattern_device, uint32_t pattern_bytes,
                           bt_flow_reasm_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes,
-                          const bt_flow_reasm_out* out, FlowreasmArgs* a, char* why, size_t cap) {
+                          const bt_flow_reasm_out* out, FlowreasmArgs* a, char* why, size_t cap, bool need_pattern = true) {
     const auto no = [&](const char* s) { snprintf(why, cap, "%s", s); return (int)BT_E_INVALID_ARGUMENT; };
     if (!frames) return no("null frames");
     if (!flowreasm_common_args(flow_id, frames->n, select, off, table_flags, table, flow_cap, out, why, cap)) return BT_E_INVALID_ARGUMENT;
-    if (!pattern_device) return no("null pattern_device");
+    if (need_pattern && !pattern_device) return no("null pattern_device");
     if (reinterpret_cast<uintptr_t>(pattern_device) & 7u) return no("pattern_device is not 8-byte aligned");
     if (reinterpret_cast<uintptr_t>(scratch) & 255u) return no("scratch is not 256-byte aligned");
     if (frames->flags & (BT_BATCH_PREFIXES | BT_BATCH_LEAN))
         return no("a BT_BATCH_PREFIXES / BT_BATCH_LEAN batch holds no whole frames to walk");
     *a = FlowreasmArgs{};
     if (frame_src(frames, a, why, cap)) return BT_E_INVALID_ARGUMENT;
-    const int prc = flowstream_pattern(pattern, pattern_bytes, &a->pat, why, cap);
+    const int prc = need_pattern ? flowstream_pattern(pattern, pattern_bytes, &a->pat, why, cap) : (int)BT_OK;   // without: bt_flow_follow_device's plain follow
     if (prc) return prc;
     const FrLayout l = fr_layout(a->n, flow_cap);
     if (a->n && !scratch) return no("null scratch");
@@ -323,5 +323,14 @@ inline void flowreasm_host(const uint8_t* base, uint64_t bytes, const bt_pkt_des
 // dispatches: the start of the classification, of the first sort, of the second sort, of the scan,
 // of the match and of the commit, and the end of the last kernel.
 int launch_flowreasm(const FlowreasmArgs& a, void* stream, void* const* ev = nullptr);
+
+// The same launches in three stages, for a caller that puts launches of its own between them
+// (bt_flowfollow.hip, which reads have and next before Commit rewrites them): the classification up
+// to Emit (ev[0 .. 3]; *sorted: the sorted pair list the later stages walk), the match (its start:
+// e4), Commit (its start and end: e5, e6). A caller that skips the match zeroes what only it writes
+// (hitw, dfin, the hit words) in stream order before Commit.
+int launch_flowreasm_front(const FlowreasmArgs& a, void* stream, void* const* ev, const FsPair** sorted);
+int launch_flowreasm_match(const FlowreasmArgs& a, void* stream, void* e4);
+int launch_flowreasm_commit(const FlowreasmArgs& a, const FsPair* sorted, void* stream, void* e5, void* e6);
 
 }  // namespace bt

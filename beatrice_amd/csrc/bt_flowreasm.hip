@@ -557,8 +557,7 @@ __global__ __launch_bounds__(kFrThreads) void bt_flowreasm_match(FlowreasmArgs a
     }
 }
 
-int launch_flowreasm(const FlowreasmArgs& a, void* stream, void* const* ev) {
-    if (a.n == 0 || a.nchunks == 0) return BT_OK;
+int launch_flowreasm_front(const FlowreasmArgs& a, void* stream, void* const* ev, const FsPair** out_sorted) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const auto e = [&](int k) { return ev ? reinterpret_cast<hipEvent_t>(ev[k]) : nullptr; };
     const dim3 grid(a.nchunks), block(kFrThreads), one(1), join(kFsJoinThreads);
@@ -585,9 +584,28 @@ int launch_flowreasm(const FlowreasmArgs& a, void* stream, void* const* ev) {
     launch(bt_flowreasm_scan<kFrCarryMode>, grid, block, 0, st, e(3), nullptr, a, sorted);
     launch(bt_flowreasm_sjoin, one, join, 0, st, nullptr, nullptr, a);
     launch(bt_flowreasm_scan<kFrEmit>, grid, block, 0, st, nullptr, nullptr, a, sorted);
-    launch(bt_flowreasm_match, grid, block, 0, st, e(4), nullptr, a);
-    launch(bt_flowreasm_scan<kFrCommit>, grid, block, 0, st, e(5), e(6), a, sorted);
+    *out_sorted = sorted;
     return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
+}
+
+int launch_flowreasm_match(const FlowreasmArgs& a, void* stream, void* e4) {
+    launch(bt_flowreasm_match, dim3(a.nchunks), dim3(kFrThreads), 0, reinterpret_cast<hipStream_t>(stream),
+           reinterpret_cast<hipEvent_t>(e4), nullptr, a);
+    return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
+}
+
+int launch_flowreasm_commit(const FlowreasmArgs& a, const FsPair* sorted, void* stream, void* e5, void* e6) {
+    launch(bt_flowreasm_scan<kFrCommit>, dim3(a.nchunks), dim3(kFrThreads), 0, reinterpret_cast<hipStream_t>(stream),
+           reinterpret_cast<hipEvent_t>(e5), reinterpret_cast<hipEvent_t>(e6), a, sorted);
+    return hipGetLastError() == hipSuccess ? BT_OK : BT_E_INTERNAL;
+}
+
+int launch_flowreasm(const FlowreasmArgs& a, void* stream, void* const* ev) {
+    if (a.n == 0 || a.nchunks == 0) return BT_OK;
+    const FsPair* sorted = nullptr;
+    if (const int rc = launch_flowreasm_front(a, stream, ev, &sorted)) return rc;
+    if (const int rc = launch_flowreasm_match(a, stream, ev ? ev[4] : nullptr)) return rc;
+    return launch_flowreasm_commit(a, sorted, stream, ev ? ev[5] : nullptr, ev ? ev[6] : nullptr);
 }
 
 }  // namespace bt

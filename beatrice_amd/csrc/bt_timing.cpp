@@ -401,6 +401,35 @@ int bt_time_flow_reasm(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_i
     return BT_OK;
 }
 
+int bt_time_flow_follow(bt_ctx* c, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select, const int64_t* off,
+                        uint32_t table_flags, const void* pattern, const void* pattern_device, uint32_t pattern_bytes,
+                        bt_flow_reasm_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes, const bt_flow_reasm_out* out,
+                        const bt_flow_follow_out* fo, uint32_t iters, float* ms, float* phase_ms) {
+    const bt::DeviceRestore keep_device;   // the caller's current device, restored on return
+    if (!c || !frames || !frames->n || !iters || !ms)
+        return set_error(BT_E_INVALID_ARGUMENT, "null argument / empty batch / zero iterations");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_timing_events(c, (9u * iters + 1u) / 2u)) return rc;
+    for (uint32_t i = 0; i < iters; ++i) {
+        void* ev[9];
+        for (uint32_t k = 0; k < 9u; ++k) ev[k] = c->timing.tev[9 * i + k];
+        if (int rc = run_flow_follow(c, frames, flow_id, select, off, table_flags, pattern, pattern_device, pattern_bytes, table, flow_cap,
+                                     scratch, scratch_bytes, out, fo, c->stream, ev)) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < iters; ++i) {
+        hipEvent_t* const e = &c->timing.tev[9 * i];
+        HIP_TRY(hipEventElapsedTime(&ms[i], e[0], e[8]));
+        if (!phase_ms) continue;
+        for (uint32_t k = 0; k < 8u; ++k) HIP_TRY(hipEventElapsedTime(&phase_ms[8 * i + k], e[k], e[k + 1]));
+    }
+    return BT_OK;
+}
+
 int bt_time_flow_top(bt_ctx* c, const void* state, const bt_flow_top_opts* opts, const bt_flow_tcp_rec* tcp, void* scratch,
                      uint64_t scratch_bytes, const bt_flow_top_out* out, uint32_t iters, float* ms) {
     const bt::DeviceRestore keep_device;   // the caller's current device, restored on return

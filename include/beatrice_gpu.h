@@ -96,7 +96,8 @@ extern "C" {
  * bt_flow_mark_select_device, bt_flow_mark_select_host, bt_flow_seq_scratch_bytes,
  * bt_flow_seq_device, bt_flow_seq_host, bt_flow_stream_compile, bt_flow_stream_scratch_bytes,
  * bt_flow_stream_device, bt_flow_stream_host, bt_flow_tcpseq_scratch_bytes, bt_flow_tcpseq_device,
- * bt_flow_tcpseq_host, bt_flow_reasm_scratch_bytes, bt_flow_reasm_device, bt_flow_reasm_host. */
+ * bt_flow_tcpseq_host, bt_flow_reasm_scratch_bytes, bt_flow_reasm_device, bt_flow_reasm_host,
+ * bt_flow_follow_scratch_bytes, bt_flow_follow_device, bt_flow_follow_host. */
 #define BT_ABI_VERSION 2
 
 /* ---- status codes (values of beatrice::ErrorCode, reference include/beatrice/Error.hpp:11-26) */
@@ -1367,6 +1368,82 @@ int  bt_flow_reasm_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* f
 int  bt_flow_reasm_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_id,
                         const uint64_t* select, const int64_t* off, uint32_t table_flags, const void* pattern,
                         uint32_t pattern_bytes, bt_flow_reasm_rec* table, uint32_t flow_cap, const bt_flow_reasm_out* out);
+
+/* ---- per-flow TCP reassembly, exported: every stream's delivered bytes in order ---------------
+ * bt_flow_reasm_device orders the segments of every (flow, direction), trims what overlaps, cuts
+ * at holes, and keeps one hit bit per packet. This call does exactly that call's work on the same
+ * bt_flow_reasm_rec table, and also writes the delivered bytes themselves: the reassembly
+ * counterpart of bt_pass_pack_device, per-flow in-order byte streams where that call gives packed
+ * frames. The arguments before `fo` are those of bt_flow_reasm_device; with a
+ * pattern, hit, rest, the table and *out->result are bit-identical to what that call writes from
+ * the same inputs. Use one of the two calls per batch on a given table, never both. On top of the
+ * rules 1. - 8. above:
+ * fo->bytes receives every delivered byte of the call, rule 6.'s [max(rel, hi), rel + len) of
+ *   every delivering segment, concatenated in ascending flow << 1 | direction and inside a stream
+ *   in rule 5.'s (rel, packet index) order. total = out->result->stream_bytes as a 64-bit count.
+ *   A byte whose output position is below fo->cap is written; nothing at or past cap is ever
+ *   written and [written, cap) is left untouched; written = min(total, cap). cap >=
+ *   frames->bytes always suffices; cap == 0 with bytes == NULL is a size query. A source byte
+ *   outside [0, frames->bytes) reads as zero, as in the host form; nothing outside the buffer is
+ *   read for the copy.
+ * fo->runs: a run is a maximal piece of one direction's stream with no hole inside. A run starts
+ *   at a stream's first delivering segment of the call and at every segment with rel > hi. Runs
+ *   are numbered in output order, so they ascend by (flow << 1 | direction, pos) and by `at`. Run
+ *   k is written iff k < run_cap, with its true `at` and `len` even where they pass cap: the
+ *   reader clips. n_runs counts all runs; runs_written = min(n_runs, run_cap). run_cap >= n
+ *   always suffices. flags: bit 0 the direction; BT_FOLLOW_NEW: the direction's record had have
+ *   == 0 when the call found it (on every run of that direction in the call); BT_FOLLOW_HOLE:
+ *   bytes are missing in front of the run (rule 6.'s hole). With neither, the run continues
+ *   exactly at the record's previous `next`. pos = base + max(rel, hi) of the run's first
+ *   segment: the unwrapped position of its first byte, in off's space.
+ * fo->place (optional, n entries): the output offset of packet i's first delivered byte, and
+ *   UINT64_MAX for every packet that delivered none (unselected and unplaced ones included).
+ * No pattern: pattern == NULL requires pattern_device == NULL and pattern_bytes == 0. No byte is
+ *   matched (the match launch is skipped), hit, where given, is written as zeros, hit_packets
+ *   and new_hit_flows are 0, and every direction the call advances gets d = 0.
+ * BT_E_INVALID_ARGUMENT before the context or any HIP call: everything bt_flow_reasm_device
+ *   refuses; a null fo or fo->result; null bytes with cap != 0; null runs with run_cap != 0;
+ *   runs, place or result not 8-byte aligned; non-zero reserved fields; [bytes, bytes + cap)
+ *   overlapping the frames' buffer; a pattern pointer given without the other, or with
+ *   pattern_bytes == 0.
+ * Asynchronous on `stream`, no allocation, no host synchronisation; n == 0 writes both results in
+ * stream order and nothing else. scratch: bt_flow_follow_scratch_bytes(n, flow_cap) bytes,
+ * 256-byte aligned. Every output is exact, equal to the host form's and bit-identical from run to
+ * run.
+ * bt_flow_follow_host: the same on the calling thread as a plain loop, which is the definition. */
+#define BT_FOLLOW_DIR   1u
+#define BT_FOLLOW_NEW   2u
+#define BT_FOLLOW_HOLE  4u
+typedef struct bt_flow_follow_run {            /* 32 B: a maximal piece of one direction's stream with no hole inside */
+    uint32_t flow;                             /* the flow id */
+    uint32_t flags;                            /* BT_FOLLOW_DIR | BT_FOLLOW_NEW | BT_FOLLOW_HOLE */
+    uint64_t at;                               /* offset of its first byte in `bytes` (whether or not it fits below cap) */
+    int64_t  pos;                              /* unwrapped position of its first byte, in off's space */
+    uint64_t len;                              /* its bytes */
+} bt_flow_follow_run;
+typedef struct bt_flow_follow_result {         /* 32 B, device-visible, 8-byte aligned */
+    uint64_t total, written;
+    uint32_t n_runs, runs_written;
+    uint64_t reserved;
+} bt_flow_follow_result;
+typedef struct bt_flow_follow_out {            /* 64 B */
+    uint8_t* bytes; uint64_t cap;
+    bt_flow_follow_run* runs; uint32_t run_cap, reserved0;
+    uint64_t* place;                           /* optional, n entries */
+    bt_flow_follow_result* result;
+    uint64_t reserved[2];
+} bt_flow_follow_out;
+
+int  bt_flow_follow_scratch_bytes(uint32_t n, uint32_t flow_cap, uint64_t* bytes);    /* host only */
+int  bt_flow_follow_device(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id /* device, n */,
+                           const uint64_t* select /* NULL = all n */, const int64_t* off /* device, n */, uint32_t table_flags,
+                           const void* pattern /* host, or NULL */, const void* pattern_device, uint32_t pattern_bytes,
+                           bt_flow_reasm_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes,
+                           const bt_flow_reasm_out* out, const bt_flow_follow_out* fo, void* stream);
+int  bt_flow_follow_host(const uint8_t* base, uint64_t bytes, const bt_pkt_desc* desc, uint32_t n, const uint32_t* flow_id,
+                         const uint64_t* select, const int64_t* off, uint32_t table_flags, const void* pattern,
+                         uint32_t pattern_bytes, bt_flow_reasm_rec* table, uint32_t flow_cap, const bt_flow_reasm_out* out,
+                         const bt_flow_follow_out* fo);
 
 /* ---- top-K flows of a tracker: the largest flows by a measure, selected on the device ------
  * bt_flow_track_top_device: the k largest flows of the tracker at `state` by opts->metric,

@@ -177,6 +177,17 @@ int  bt_time_flow_reasm(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flo
                         uint32_t table_flags, const void* pattern, const void* pattern_device, uint32_t pattern_bytes,
                         bt_flow_reasm_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes,
                         const bt_flow_reasm_out* out, uint32_t iters, float* ms, float* phase_ms);
+/* bt_flow_follow_device `iters` times on the context's stream into the same table and the same
+ * scratch and outputs (zero the table between launches by calling with iters = 1); ms[i] = call i's
+ * kernels, from the first one's start to the last one's end (the memsets in front are outside, those
+ * of the no-pattern mode inside). phase_ms (optional, 8 * iters): call i's classification +
+ * compaction, first sort, rekey + second sort, carry scan + join + emit, match (without a pattern:
+ * the memsets that stand in for it), the follow's sums + join + emit + runs, its copy, and commit,
+ * in that order. */
+int  bt_time_flow_follow(bt_ctx* ctx, const bt_batch* frames, const uint32_t* flow_id, const uint64_t* select, const int64_t* off,
+                         uint32_t table_flags, const void* pattern, const void* pattern_device, uint32_t pattern_bytes,
+                         bt_flow_reasm_rec* table, uint32_t flow_cap, void* scratch, uint64_t scratch_bytes,
+                         const bt_flow_reasm_out* out, const bt_flow_follow_out* fo, uint32_t iters, float* ms, float* phase_ms);
 /* What the tracker replaces, `iters` times: copy_ms[i] = the n_flows records of a per-batch table
  * (flows, on the device) copied to pinned host memory (wall clock, the wait included), merge_ms[i]
  * = those records merged into the host tracker state at host_state (bt_flow_track_init_host's) on
